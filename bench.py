@@ -19,8 +19,14 @@ frame overlaps the bulk of the next ones, as a viewer that double-buffers its di
 of the K timed steps is still a complete frame (render, gather, un-permute) and all of them finish inside the timed
 region.  Default: D = 1 on one GPU (each frame is synchronised, like the reference's render(); this is the run
 the roofline and the rocprof summaries refer to), 4 on 2-4 GPUs, 8 on 8.  So that a scaling curve compares like
-with like, EVERY run reports both figures next to `value`: `config.value_sync` (D = 1, every frame synchronised)
+with like, every --full run reports both figures next to `value`: `config.value_sync` (D = 1, every frame synchronised)
 and `config.value_pipelined` (D = 4, or 8 from 8 GPUs on), each over its own K timed frames.
+
+A plain run does only what the headline needs: set-up, three settling frames and one frame with the ray counters on
+(`value` counts the rays that frame traced), W warm-up and K timed steps, the result line.  --full adds everything
+else this script measures, outside the timed region: the cold-frame and moving-camera legs, the other pipelining
+depth, the settled memory of slot 0, and the CPU oracle's baseline and parity check of the frame (`cpu_baseline`,
+`parity`).  --dump-outputs DIR writes the frame of the last timed step as DIR/frame.npy (float32, values 0..255).
 
 The step machinery (frame slots, tile split, gather, un-permute) is class FrameLoop: bench.py drives it with the HIP
 library over RCCL, tests/test_multi_rank_cpu.py drives the same class with the CPU oracle over gloo.
@@ -178,8 +184,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--sh-degree", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the untimed legs (cold frame, orbit, the other pipelining depth)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs (cold frame, orbit, the other pipelining depth) and the CPU baseline + parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline + parity check")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the untimed legs (cold frame, orbit, the other pipelining depth)")
     ap.add_argument("--kernel", type=int, default=0, help="traversal kernel variant (GRT_OPT_KERNEL)")
     ap.add_argument("--split", type=int, default=-1, help="GRT_OPT_SPLIT (piece length of the spatial splits, quarters of the typical proxy diagonal; 0 = off; -1 = library default)")
     ap.add_argument("--leaf-max", type=int, default=0, help="GRT_OPT_LEAF_MAX before the BVH is built (0 = library default)")
@@ -188,6 +196,8 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="ID=VALUE",
                     help="grt_set_option(ID, VALUE) on every frame slot (tuning sweeps; include/grt.h lists the options), repeatable")
     ap.add_argument("--dump", default=None, help="write the frame as .npy (rank 0)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame of the last timed step as DIR/frame.npy, float32 (rank 0)")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="one process, one GPU: do the work of ONE rank of an N-rank run (tile list, frame slots, "
                          "un-permute; the collective is replaced by a local copy) - per-rank time without N GPUs")
@@ -200,6 +210,9 @@ def main():
     args = ap.parse_args()
     if args.tile <= 0 or args.tile % 16:
         print("bench.py: --tile must be a positive multiple of 16", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         sys.exit(2)
     TILE = args.tile
 
@@ -239,7 +252,7 @@ def main():
                            max_bounces=max_bounces)
     D_pipe = 8 if t_world >= 8 else 4
     D = args.inflight if args.inflight > 0 else (1 if t_world == 1 else D_pipe)
-    extra = not args.no_extra_legs
+    extra = args.full and not args.no_extra_legs
     D_other = (D_pipe if D == 1 else 1) if extra else 0  # the other pipelining depth, reported alongside
     n_ctx = max(D, D_other)
     t0 = time.time()
@@ -371,7 +384,10 @@ def main():
         return el, latency, kms
 
     elapsed, latency_ms, kern_ms = timed(loop, args.steps, args.warmup)
-    if D > 1:
+    outputs = None
+    if args.dump_outputs and rank == 0:  # what the last timed step computed, before any later leg reuses the slot's frame
+        outputs = {"frame": loop.frames[(args.steps - 1) % D].cpu().numpy().astype(np.float32)}
+    if D > 1 and args.full:
         # kernel duration for the roofline: synchronous launches of the same frame right after the timed region
         # (the launches inside it overlap each other, so their own durations are not launch durations)
         for _ in range(4):
@@ -422,12 +438,12 @@ def main():
             tr.sync()
     mem_settled = tr.memory_info()
     el = torch.tensor([elapsed, other[0] if other else 0.0], dtype=torch.float64, device=dev)
-    km = torch.tensor([float(np.mean(kern_ms))], dtype=torch.float64, device=dev)
+    km = torch.tensor([float(np.mean(kern_ms)) if kern_ms else float("nan")], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         dist.all_reduce(km, op=dist.ReduceOp.MAX)
     elapsed, elapsed_other = float(el[0].item()), float(el[1].item())
-    kernel_ms = float(km.item())
+    kernel_ms = None if np.isnan(km.item()) else float(km.item())  # (a plain run of D > 1 frames in flight times no single launch)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -439,7 +455,7 @@ def main():
         b_alg = contract_bytes(cnt, pix_mine, args.sh_degree)       # H * B_hit + V * 32 + P * 3
         b_fetch = algorithmic_bytes(cnt, pix_mine, args.sh_degree)  # as fetched (records are shared by a wave: below the floor)
         b_min = cnt["hit_evals"] * (44 + 12 * (args.sh_degree + 1) ** 2) + pix_mine * 3  # SURVEY §8(d) floor
-        achieved = b_alg / (kernel_ms * 1e-3) / 1e9
+        achieved = None if kernel_ms is None else b_alg / (kernel_ms * 1e-3) / 1e9
         traffic = valu = traffic_source = traffic_round = None
         kname = kernel_name(args.kernel, with_mesh, args.sh_degree, pieces=info["n_primitives"] > info["n_proxies"])
         tpath = os.path.join(ROOT, TRAFFIC_FILE)
@@ -508,8 +524,8 @@ def main():
                        "frame_ms_cold": None if cold_wall_ms is None else round(cold_wall_ms, 4),
                        "kernel_ms_cold_screen_order": None if cold_screen_ms is None else round(cold_screen_ms, 4),
                        "kernel_ms_orbit": None if orbit_ms is None else round(orbit_ms, 4)},
-            "kernel_ms": round(kernel_ms, 4),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "kernel_ms": None if kernel_ms is None else round(kernel_ms, 4),
+            "roofline": None if kernel_ms is None else {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
                          "traffic_collected_round": traffic_round,
                          "kernel": kname, "algorithmic_bytes_per_launch": int(b_alg),
@@ -522,8 +538,8 @@ def main():
                          "kernel_ms_median": round(float(np.median(kern_ms)), 4), "kernel_ms_min": round(float(np.min(kern_ms)), 4),
                          "valu_issue": valu},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            # the oracle's frame is the CHECKER of this run's GPU frame as well as the baseline: every bench line carries its own
+        if world == 1 and args.full and not args.no_cpu_baseline:
+            # the oracle's frame is the CHECKER of this run's GPU frame as well as the baseline: every --full bench line carries its own
             # correctness figure.  Outside every timed region; the product path never calls it.
             g8 = gf = None
             if t_world == 1:
@@ -533,6 +549,10 @@ def main():
             out["cpu_baseline"], out["parity"] = cpu_baseline(acts, p, mesh, W, H, g8, gf)
         if args.dump:
             np.save(args.dump, frame.cpu().numpy())
+        if outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

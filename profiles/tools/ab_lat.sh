@@ -1,6 +1,6 @@
 #!/bin/bash
 # latency-bound cases per variant library: C1, C2 static kernel + orbit frame, rank 4 of 8 synchronous
-run() { L=$1; shift; GRT_LIB=$PWD/gaussian-ray-tracing_amd/libgrt_hip_$L.so python bench.py --steps 20 --warmup 6 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+run() { L=$1; shift; GRT_LIB=$PWD/gaussian-ray-tracing_amd/libgrt_hip_$L.so python bench.py --steps 20 --warmup 6 --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ ARGS=()
 while [ "$1" != "--" ]; do ARGS+=("$1"); shift; done
 shift
 for O in "$@"; do
-  python bench.py "${ARGS[@]}" --no-cpu-baseline $O 2>> $OUT.err | python -c "
+  python bench.py "${ARGS[@]}" --full --no-cpu-baseline $O 2>> $OUT.err | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,6 +1,6 @@
 """Pins the CPU oracle (oracle/grt_oracle.c) function by function:
  (a) against the probe values the reference's own device code printed (tests/golden/survey_probes.json),
- (b) bit-for-bit against oracle/_ref (reference sources compiled in place) where that library exists,
+ (b) bit-for-bit against oracle/_ref (reference sources compiled in place), through its outputs stored in tests/golden/ref_pins.npz,
  (c) against the analytic known-answer tests of SURVEY.md §4.2."""
 import ctypes as C
 import json
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+import ref_pins as P
 
 G = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "survey_probes.json")))
 fp = C.POINTER(C.c_float)
@@ -206,108 +207,72 @@ def test_origin_inside_proxy_gives_exit_only():
 
 
 # ---------------------------------------------------------------------------------------------
-# bit-exact pins against the reference sources compiled in place (oracle/_ref)
+# bit-exact pins against the reference sources compiled in place (oracle/_ref): the reference's outputs for the pins' seeded
+# inputs are stored in tests/golden/ref_pins.npz (oracle/ref_pins.py writes it), so the pins hold where oracle/_ref was never built
 # ---------------------------------------------------------------------------------------------
+REF = np.load(P.GOLDEN)
 needs_ref = pytest.mark.skipif(not os.path.exists(O._REF), reason="oracle/_ref/libgrt_ref.so not built")  # (file check only: the .so is loaded by the CPU tests that use it, never at collection)
 
 
 @needs_ref
+def test_ref_pins_golden_equals_the_reference_library():
+    """tests/golden/ref_pins.npz is what the reference library built here returns for the same inputs, bit for bit."""
+    live = P.compute(O.ref(), O.lib())
+    assert sorted(live) == sorted(REF.files)
+    for k, v in live.items():
+        assert v.tobytes() == REF[k].tobytes(), k
+
+
 def test_ref_uvw_frame_bitexact():
-    rng = np.random.default_rng(7)
-    R = O.ref()
-    for _ in range(200):
-        eye = f32(rng.normal(size=3) * 3); look = f32(rng.normal(size=3)); up = f32([0, 1, 0])
-        fov = float(rng.uniform(20, 100)); asp = float(rng.uniform(0.5, 2.5))
+    for (eye, look, up, fov, asp), want in zip(P.uvw_inputs(), REF["uvw"]):
         U, V, W = O.uvw_frame(eye, look, up, fov, asp)
-        u2 = np.zeros(3, np.float32); v2 = np.zeros(3, np.float32); w2 = np.zeros(3, np.float32)
-        R.ref_uvw_frame(ptr(eye), ptr(look), ptr(up), C.c_float(fov), C.c_float(asp), ptr(u2), ptr(v2), ptr(w2))
-        assert U.tobytes() == u2.tobytes() and V.tobytes() == v2.tobytes() and W.tobytes() == w2.tobytes()
+        assert U.tobytes() == want[0].tobytes() and V.tobytes() == want[1].tobytes() and W.tobytes() == want[2].tobytes()
 
 
-@needs_ref
 def test_ref_icosahedron_bitexact():
     v = np.zeros((12, 3), np.float32); idx = np.zeros(60, np.uint32)
     O.lib().grto_icosahedron(v.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p))
-    v2 = np.zeros(36, np.float32); i2 = np.zeros(60, np.uint32)
-    O.ref().ref_icosahedron(ptr(v2), i2.ctypes.data_as(C.c_void_p))
-    assert v.tobytes() == v2.tobytes() and idx.tobytes() == i2.tobytes()
+    assert v.tobytes() == REF["icosahedron_vertices"].tobytes() and idx.tobytes() == REF["icosahedron_indices"].tobytes()
 
 
-@needs_ref
 def test_ref_glm_invcov_and_matvec_bitexact():
-    rng = np.random.default_rng(11)
-    R = O.ref(); L = O.lib()
-    for _ in range(300):
-        p = np.zeros(1, O.PARTICLE_DTYPE)
-        q = f32(rng.normal(size=4)); q = f32(q / np.float32(np.sqrt(np.float32((q * q).sum()))))
-        p["quat"] = q; p["scale"] = f32(np.exp(rng.normal(-3, 1, size=3))); p["pos"] = f32(rng.normal(size=3))
-        A = np.zeros(9, np.float32); A2 = np.zeros(9, np.float32)
+    L = O.lib()
+    for p, A2, Rg2 in zip(P.invcov_inputs(), REF["inv_cov"], REF["mat3_cast"]):
+        A = np.zeros(9, np.float32)
         L.grto_inv_cov(C.c_void_p(p.ctypes.data), ptr(A))
-        sc = f32(p["scale"][0]); qq = f32(p["quat"][0])
-        R.ref_inv_cov(ptr(sc), ptr(qq), ptr(A2))
         assert A.tobytes() == A2.tobytes()
-        Rg = np.zeros(9, np.float32); Rg2 = np.zeros(9, np.float32)
-        L.grto_mat3_cast(ptr(qq), ptr(Rg)); R.ref_mat3_cast(ptr(qq), ptr(Rg2))
+        Rg = np.zeros(9, np.float32)
+        L.grto_mat3_cast(ptr(f32(p["quat"][0])), ptr(Rg))
         assert Rg.tobytes() == Rg2.tobytes()
 
 
-@needs_ref
 def test_ref_response_chain_bitexact():
     """computeResponse rebuilt from the reference's glm pieces (mat*vec, dot) equals the oracle's value."""
-    rng = np.random.default_rng(13)
-    R = O.ref(); L = O.lib()
-    for _ in range(200):
-        p = np.zeros(1, O.PARTICLE_DTYPE)
-        q = f32(rng.normal(size=4)); q = f32(q / np.float32(np.sqrt(np.float32((q * q).sum()))))
-        p["quat"] = q; p["scale"] = f32(np.exp(rng.normal(-2, 0.7, size=3))); p["pos"] = f32(rng.normal(size=3) * 0.3)
-        o = f32([0, 0, 3]); d = f32(rng.normal(size=3) * 0.1 + [0, 0, -1])
-        dn = np.zeros(3, np.float32); R.ref_normalize(ptr(d), ptr(dn))
-        A = np.zeros(9, np.float32)
-        R.ref_inv_cov(ptr(f32(p["scale"][0])), ptr(f32(p["quat"][0])), ptr(A))
-        mu = f32(p["pos"][0])
-        og = np.zeros(3, np.float32); dg = np.zeros(3, np.float32); pg = np.zeros(3, np.float32)
-        R.ref_mat3_vec(ptr(A), ptr(f32(o - mu)), ptr(og)); R.ref_mat3_vec(ptr(A), ptr(dn), ptr(dg))
-        dval = np.float32(-np.float32(R.ref_glm_dot(ptr(og), ptr(dg))) / max(np.float32(1e-6), np.float32(R.ref_glm_dot(ptr(dg), ptr(dg)))))
-        pos = f32(o + f32(dval * dn))
-        R.ref_mat3_vec(ptr(A), ptr(f32(mu - pos)), ptr(pg))
-        expect_arg = np.float32(np.float32(-0.5) * np.float32(R.ref_glm_dot(ptr(pg), ptr(pg))))
-        got = L.grto_compute_response(p.ctypes.data, ptr(o), ptr(dn))
+    L = O.lib()
+    for (p, o, _), dn, expect_arg in zip(P.response_inputs(), REF["response_dir"], REF["response_exp_arg"]):
+        got = L.grto_compute_response(p.ctypes.data, ptr(o), ptr(f32(dn)))
         # same argument bit-for-bit => same expf(); compare through log to avoid libm identity assumptions
         assert abs(got - float(np.exp(np.float64(expect_arg)))) <= 1.2e-7 * max(1.0, got)
 
 
-@needs_ref
 def test_ref_vector_math_bitexact():
-    rng = np.random.default_rng(5)
-    R = O.ref(); L = O.lib()
-    for _ in range(200):
-        a = f32(rng.normal(size=3)); n = f32(rng.normal(size=3))
-        nn = np.zeros(3, np.float32); R.ref_normalize(ptr(n), ptr(nn))
-        r1 = np.zeros(3, np.float32); r2 = np.zeros(3, np.float32)
-        L.grto_reflect(ptr(a), ptr(nn), ptr(r1)); R.ref_reflect(ptr(a), ptr(nn), ptr(r2))
+    L = O.lib()
+    for (a, _), nn, r2 in zip(P.vector_inputs(), REF["normalized"], REF["reflected"]):
+        r1 = np.zeros(3, np.float32)
+        L.grto_reflect(ptr(a), ptr(f32(nn)), ptr(r1))
         assert r1.tobytes() == r2.tobytes()
 
 
-@needs_ref
 def test_ref_proxy_vertices_inside_oracle_aabb_and_on_slab_planes():
     """The reference instance transform T*(R*S) puts the 12 proxy vertices where the oracle's slab
     polytope has its vertices: every vertex satisfies max_i |n_i.A(v-mu)| == s (to rounding)."""
-    rng = np.random.default_rng(3)
-    R = O.ref(); L = O.lib()
-    v = np.zeros((12, 3), np.float32); idx = np.zeros(60, np.uint32)
-    L.grto_icosahedron(v.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p))
+    L = O.lib()
     n = np.zeros((10, 3), np.float32); L.grto_slab_normals(n.ctypes.data_as(C.c_void_p))
-    for _ in range(50):
-        p = np.zeros(1, O.PARTICLE_DTYPE)
-        q = f32(rng.normal(size=4)); q = f32(q / np.float32(np.sqrt(np.float32((q * q).sum()))))
-        p["quat"] = q; p["scale"] = f32(np.exp(rng.normal(-2, 0.7, size=3))); p["pos"] = f32(rng.normal(size=3))
-        p["opacity"] = 0.6
-        s = L.grto_proxy_scale(0.6, 0.01)
+    s = L.grto_proxy_scale(0.6, 0.01)
+    for p, ws in zip(P.proxy_inputs(), REF["proxy_vertices"]):
         A = np.zeros(9, np.float32); L.grto_inv_cov(C.c_void_p(p.ctypes.data), ptr(A))
         A = A.reshape(3, 3).astype(np.float64)
-        for k in range(12):
-            w = np.zeros(3, np.float32)
-            R.ref_instance_vertex(ptr(f32(p["pos"][0])), ptr(f32(p["scale"][0])), ptr(f32(p["quat"][0])), C.c_float(s), ptr(v[k]), ptr(w))
+        for w in ws:
             g = A @ (w.astype(np.float64) - p["pos"][0].astype(np.float64))
             m = np.max(np.abs(n.astype(np.float64) @ g))
             assert abs(m - s) < 2e-3 * s
@@ -317,44 +282,28 @@ def test_ref_proxy_vertices_inside_oracle_aabb_and_on_slab_planes():
 # decision (v) on whole frames: ten slabs in Gaussian space == the reference's 20 instanced triangles
 # ---------------------------------------------------------------------------------------------
 def _small_scene(n=300, seed=21):
-    rng = np.random.default_rng(seed)
-    pos = f32(rng.normal(0.0, 0.45, size=(n, 3)))
-    f_dc = f32(rng.uniform(-1.5, 1.5, size=(n, 3)))
-    f_rest = f32(rng.normal(0.0, 0.1, size=(n, 45)))
-    logit = f32(rng.normal(1.0, 2.0, size=n))
-    log_scale = f32(rng.normal(np.log(0.12), 0.6, size=(n, 3)))  # anisotropic: axes differ by e^(+-0.6)
-    rot = f32(rng.normal(size=(n, 4)))
-    return O.activate(pos, f_dc, f_rest, logit, log_scale, rot)
+    return P.small_scene(n, seed)
 
 
 def _ref_instanced_icosahedra(parts, alpha_min=0.01):
     """World-space vertices [n][12][3] of every particle's proxy: the reference's OWN mesh (src/geometry/Icosahedron.h:13-37) through the
     reference's OWN instance transform T * (R * S) (src/GaussianTracer.cpp:304-311: glm translate / mat4_cast / scale with
-    s = sqrtf(2 logf(opacity / alpha_min)), :306), both compiled from the reference's sources in oracle/_ref."""
-    R = O.ref()
-    base = np.zeros(36, np.float32); idx = np.zeros(60, np.uint32)
-    R.ref_icosahedron(ptr(base), idx.ctypes.data_as(C.c_void_p))
-    base = base.reshape(12, 3)
-    out = np.zeros((len(parts), 12, 3), np.float32)
-    for i, p in enumerate(parts):
-        if not p["opacity"] > alpha_min:
-            continue  # NaN / zero transform in the reference: unhittable (decision (vi)); the oracle never tests it
-        s = np.float32(np.sqrt(np.float32(2.0) * np.float32(np.log(np.float32(p["opacity"] / np.float32(alpha_min))))))
-        assert abs(float(s) - O.lib().grto_proxy_scale(float(p["opacity"]), alpha_min)) <= 2e-7 * float(s)
-        for k in range(12):
-            w = np.zeros(3, np.float32)
-            R.ref_instance_vertex(ptr(f32(p["pos"])), ptr(f32(p["scale"])), ptr(f32(p["quat"])), C.c_float(float(s)), ptr(f32(base[k])), ptr(w))
-            out[i, k] = w
-    return out, idx
+    s = sqrtf(2 logf(opacity / alpha_min)), :306), both compiled from the reference's sources in oracle/_ref and stored for
+    these particles in tests/golden/ref_pins.npz."""
+    assert parts.tobytes() == REF["small_scene_particles"].tobytes(), "not the particles the stored vertices were computed for"
+    for p in parts:
+        if p["opacity"] > alpha_min:
+            s = P.proxy_scale(p["opacity"], alpha_min)
+            assert abs(float(s) - O.lib().grto_proxy_scale(float(p["opacity"]), alpha_min)) <= 2e-7 * float(s)
+    return REF["instanced_icosahedra"].copy(), REF["icosahedron_indices"].copy()
 
 
-@needs_ref
 @pytest.mark.parametrize("mode", ["pinhole", "fisheye", "mirror", "glass_sh2"])
 def test_decision_v_slabs_equal_the_reference_built_triangles_on_whole_frames(mode):
     """SURVEY 8(c) decision (v) replaces OptiX's ray / triangle tests against the instanced icosahedron by ten slab tests in Gaussian
     space; until round 6 the only evidence for it on whole frames was a probe the survey session ran.  Here the oracle renders small
     frames twice: with the slabs, and with every proxy intersected as its 20 TRIANGLES — vertices from the reference's own mesh and
-    instance transform (oracle/_ref), double-precision Moeller-Trumbore, no culling, brute force over all particles (no BVH of ours
+    instance transform (oracle/_ref, stored), double-precision Moeller-Trumbore, no culling, brute force over all particles (no BVH of ours
     in the way) — feeding the same k-buffer and integrator (shaders/tracer.cu:136-153, tracer.cuh:328-373).  0 differing 8-bit
     levels, radiance within 1e-6, identical hit counts."""
     parts = _small_scene()
