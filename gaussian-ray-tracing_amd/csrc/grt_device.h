@@ -264,19 +264,20 @@ __device__ __forceinline__ void get_ray(uint32_t ix, uint32_t iy, f3 U, f3 V, f3
     dir = normalize3(add3(add3(mul3s(U, dx), mul3s(V, dy)), W));
 }
 
-// getFishEyeRay — shaders/tracer.cuh:136-165; r > 1 => no ray (decision vii)
+// getFishEyeRay — shaders/tracer.cuh:136-165; r > 1 => no ray (decision vii).  theta = 2 asin(r / sqrt 2), phi = atan2(dy, dx)
+// without trig: cos theta = 1 - s, sin theta = r sqrt(2 - s), cos phi = dx / r, sin phi = dy / r (s = r^2), so the direction is
+// (dx sqrt(2 - s), dy sqrt(2 - s), 1 - s).  Only + - * and sqrtf (correctly rounded, no contraction): the same bits as
+// oracle/grt_oracle.c grto_get_fisheye_ray
 __device__ __forceinline__ bool get_fisheye_ray(uint32_t ix, uint32_t iy, f3 U, f3 V, f3 W, uint32_t width,
                                                 uint32_t height, f3& dir)
 {
     const float dx = 2.0f * (((float)ix + 0.5f) / (float)(int)width) - 1.0f;
     const float dy = 2.0f * (((float)iy + 0.5f) / (float)(int)height) - 1.0f;
-    const float r = sqrtf(dx * dx + dy * dy);
+    const float s = dx * dx + dy * dy;
+    const float r = sqrtf(s);
     if (r > 1.0f) return false;
-    const float f = 1.0f / sqrtf(2.0f);
-    const float theta = 2.0f * asinf(r / (2.0f * f));
-    const float phi = atan2f(dy, dx);
-    const f3 d = mk3(sinf(theta) * cosf(phi), sinf(theta) * sinf(phi), cosf(theta));
-    dir = normalize3(add3(add3(mul3s(U, d.x), mul3s(V, d.y)), mul3s(W, d.z)));
+    const float q = sqrtf(2.0f - s);
+    dir = normalize3(add3(add3(mul3s(U, dx * q), mul3s(V, dy * q)), mul3s(W, 1.0f - s)));
     return true;
 }
 

@@ -213,19 +213,21 @@ void grto_get_ray(uint32_t ix, uint32_t iy, const float U[3], const float V[3], 
 }
 
 /* a7: getFishEyeRay — shaders/tracer.cuh:136-165.  r > 1: the reference returns without writing
- * the ray (UB); decision (vii): no ray, black pixel -> return 0. */
+ * the ray (UB); decision (vii): no ray, black pixel -> return 0.
+ * The reference's theta = 2 asin(r / sqrt 2), phi = atan2(dy, dx) without trig: with s = r^2,
+ * cos theta = 1 - s, sin theta = r sqrt(2 - s), cos phi = dx / r, sin phi = dy / r, so the direction is
+ * (dx sqrt(2 - s), dy sqrt(2 - s), 1 - s) — (0, 0, 1) at r = 0.  Only + - * and sqrtf (correctly rounded on
+ * host and device, no contraction): grt_device.h get_fisheye_ray computes the same bits. */
 int grto_get_fisheye_ray(uint32_t ix, uint32_t iy, const float U[3], const float V[3], const float W[3],
                          const float eye[3], uint32_t width, uint32_t height, float o[3], float d[3])
 {
     const float dx = 2.0f * (((float)ix + 0.5f) / (float)(int)width) - 1.0f;
     const float dy = 2.0f * (((float)iy + 0.5f) / (float)(int)height) - 1.0f;
-    const float r = sqrtf(dx * dx + dy * dy);
+    const float s = dx * dx + dy * dy;
+    const float r = sqrtf(s);
     if (r > 1.0f) return 0;
-    const float f = 1.0f / sqrtf(2.0f);
-    const float theta = 2.0f * asinf(r / (2.0f * f));
-    const float phi = atan2f(dy, dx);
-    const f3 dir = mk3(sinf(theta) * cosf(phi), sinf(theta) * sinf(phi), cosf(theta));
-    f3 w = add3(add3(mul3s(ld3(U), dir.x), mul3s(ld3(V), dir.y)), mul3s(ld3(W), dir.z));
+    const float q = sqrtf(2.0f - s);
+    f3 w = add3(add3(mul3s(ld3(U), dx * q), mul3s(ld3(V), dy * q)), mul3s(ld3(W), 1.0f - s));
     st3(o, ld3(eye));
     st3(d, normalize3(w));
     return 1;
@@ -981,6 +983,30 @@ static inline void add_counters(grto_counters* a, const grto_counters* b)
 {
     a->rays += b->rays; a->segments += b->segments; a->hit_evals += b->hit_evals; a->rounds += b->rounds;
     a->node_visits += b->node_visits; a->proxy_tests += b->proxy_tests;
+}
+
+uint64_t grto_camera_rays(const grto_params* prm, float* rays, uint8_t* valid)
+{
+    const float nU[3] = {-prm->U[0], -prm->U[1], -prm->U[2]}, nV[3] = {-prm->V[0], -prm->V[1], -prm->V[2]};
+    const int64_t h = prm->height;
+    uint64_t n = 0;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) reduction(+ : n)
+#endif
+    for (int64_t y = 0; y < h; y++)
+        for (uint32_t x = 0; x < prm->width; x++) {
+            const size_t pi = (size_t)y * prm->width + x;
+            float* r = &rays[pi * 6];
+            int ok = 1;
+            if (!prm->mode_fisheye)
+                grto_get_ray(x, (uint32_t)y, nU, nV, prm->W, prm->eye, prm->width, prm->height, r, r + 3);
+            else
+                ok = grto_get_fisheye_ray(x, (uint32_t)y, nU, nV, prm->W, prm->eye, prm->width, prm->height, r, r + 3);
+            if (!ok) memset(r, 0, 6 * sizeof(float));
+            valid[pi] = (uint8_t)ok;
+            n += (uint64_t)ok;
+        }
+    return n;
 }
 
 void grto_render(const grto_scene* s, const grto_params* prm, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,

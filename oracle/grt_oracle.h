@@ -108,6 +108,9 @@ void grto_trace(const grto_scene* s, const grto_params* prm, const float o[3], c
 /* full raygen state machine for one pixel (tracer.cu:17-110) -> pre-clamp accumColor */
 void grto_render_pixel(const grto_scene* s, const grto_params* prm, uint32_t ix, uint32_t iy, float rgb[3],
                        grto_counters* c);
+/* the primary rays of every pixel exactly as grto_render_pixel spawns them (raygen with -U, -V, W):
+ * rays[h][w][6] = o,d row-major, valid[h][w] = 1 where a ray exists (0: fisheye r > 1, ray zeroed); returns the count */
+uint64_t grto_camera_rays(const grto_params* prm, float* rays, uint8_t* valid);
 /* window [x0,x1) x [y0,y1); out_u8/out_f32 are FULL-FRAME row-major buffers (either may be NULL) */
 void grto_render(const grto_scene* s, const grto_params* prm, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
                  uint8_t* out_u8, float* out_f32, grto_counters* c, int n_threads);

@@ -77,6 +77,8 @@ def lib():
         L.grto_refract.restype = C.c_int
         L.grto_refract.argtypes = [fp, fp, C.c_float, fp]
         L.grto_get_fisheye_ray.restype = C.c_int
+        L.grto_camera_rays.restype = C.c_uint64
+        L.grto_camera_rays.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p]
         L.grto_tri_hit.restype = C.c_int
         _lib = L
     return _lib
@@ -132,6 +134,16 @@ def make_params(width, height, eye, U, V, W, sh_degree=0, fisheye=False, mesh_ty
     p.t_min, p.t_max, p.min_transmittance, p.alpha_min = t_min, t_max, min_transmittance, alpha_min
     p.mode_fisheye, p.type, p.max_bounces = int(fisheye), mesh_type, max_bounces
     return p
+
+
+def camera_rays(params):
+    """The primary ray of every pixel as the oracle's frame spawns it: (rays [h, w, 6] float32 = o, d; valid [h, w] bool).
+    Fisheye pixels with r > 1 have no ray (valid False, zeros)."""
+    w, h = params.width, params.height
+    rays = np.zeros((h, w, 6), np.float32)
+    valid = np.zeros((h, w), np.uint8)
+    lib().grto_camera_rays(C.byref(params), rays.ctypes.data, valid.ctypes.data)
+    return rays, valid.astype(bool)
 
 
 def uvw_frame(eye, lookat, up, fovy, aspect):

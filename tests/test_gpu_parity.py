@@ -115,8 +115,8 @@ def test_dense_large_proxies_many_rounds(tr):
 
 
 def test_fisheye(tr):
-    """Fisheye raygen uses sinf/cosf/asinf/atan2f whose device/host ulps differ: ray directions differ in the
-    last bits, so allow a 2e-4 fraction of near-tie order flips (SURVEY §7 hard part 1)."""
+    """Fisheye frames are held to the pinhole rule: the raygen uses only + - * sqrtf (grt_device.h get_fisheye_ray), so device and
+    oracle rays are the same bits (test_fisheye_exact_with_host_rays) and every pixel is within 1e-4."""
     acts, p, sc, op, _ = make_scene(7, 4000, 128, 96, scale_boost=0.5, fisheye=True)
     tr.upload(acts)
     tr.set_option(grt.OPT_COUNTERS, 1)
@@ -124,32 +124,43 @@ def test_fisheye(tr):
     cnt = tr.counters()
     tr.set_option(grt.OPT_COUNTERS, 0)
     ref_u8, ref_f32, rc = sc.render(op)
-    compare(f32, ref_f32, u8, ref_u8, max_outlier_frac=2e-4, max_outlier=0.08)
+    compare(f32, ref_f32, u8, ref_u8)
     assert cnt["rays"] == rc["rays"] < 128 * 96
+    assert abs(cnt["hit_evals"] - rc["hit_evals"]) <= 1e-4 * rc["hit_evals"]
     g = f32.cpu().numpy()
     assert (g[0, 0] == 0).all() and (u8.cpu().numpy()[0, 0] == 0).all()  # r > 1 => black (decision vii)
 
 
-def test_fisheye_exact_with_host_rays(tr):
-    """Ray-buffer mode: with the oracle's own fisheye rays the integration is bit-reproducible."""
-    import ctypes as C
+def camera_rays_equal_the_oracle_rays(tr, seed, n, W, H, fisheye):
+    """The camera-ray frame (raygen on the device, on the fixture's kernel) against the ray-buffer frame of the oracle's own
+    camera rays (grto_camera_rays, the rays grto_render_pixel spawns; ray buffers run on the per-lane kernel, bit-identical to
+    the others): on every pixel with a ray the two float32 radiances are EQUAL, so device raygen == oracle raygen to the bit
+    (a ray that moved by one ulp changes the radiance's low bits on nearly every covered pixel).  The ray-buffer frame is
+    also the oracle's within 1e-4, and pixels without a ray are black."""
     import torch
-    acts, p, sc, op, _ = make_scene(7, 4000, 64, 48, scale_boost=0.5, fisheye=True)
+    acts, p, sc, op, _ = make_scene(seed, n, W, H, scale_boost=0.5, fisheye=fisheye)
     tr.upload(acts)
-    L = O.lib(); fp = C.POINTER(C.c_float)
-    L.grto_get_fisheye_ray.argtypes = [C.c_uint32, C.c_uint32, fp, fp, fp, fp, C.c_uint32, C.c_uint32, fp, fp]
-    nU = np.float32([-x for x in p.U]); nV = np.float32([-x for x in p.V]); W = np.float32(list(p.W)); eye = np.float32(list(p.eye))
-    rays = []
-    for y in range(48):
-        for x in range(64):
-            o = np.zeros(3, np.float32); d = np.zeros(3, np.float32)
-            if L.grto_get_fisheye_ray(x, y, nU.ctypes.data_as(fp), nV.ctypes.data_as(fp), W.ctypes.data_as(fp),
-                                      eye.ctypes.data_as(fp), 64, 48, o.ctypes.data_as(fp), d.ctypes.data_as(fp)):
-                rays.append(np.concatenate([o, d]))
-    rays = np.float32(rays)
-    ref, _ = sc.render_rays(op, rays)
-    out = tr.render_rays(p, torch.tensor(rays, device="cuda:0"))
+    _, f32 = tr.render(p, want_u8=False, want_f32=True)
+    g = f32.cpu().numpy()
+    rays, valid = O.camera_rays(op)
+    assert (0.7 * W * H < valid.sum() < W * H) if fisheye else valid.all()
+    rr = rays[valid]
+    out = tr.render_rays(p, torch.tensor(rr, device="cuda:0")).cpu().numpy()
+    ref, _ = sc.render_rays(op, rr)
     compare(out, ref)
+    diff = (g[valid].view(np.uint32) != out.view(np.uint32)).any(-1)
+    assert not diff.any(), f"{int(diff.sum())} of {len(rr)} pixels: camera frame != oracle-ray frame, e.g. {np.argwhere(valid)[diff][:4].tolist()}"
+    assert (g[~valid] == 0).all()
+    assert (np.abs(g[valid]).sum(-1) > 0).mean() > 0.25  # the rays do meet the cloud
+    sc.close()
+
+
+def test_fisheye_exact_with_host_rays(tr):
+    camera_rays_equal_the_oracle_rays(tr, 7, 4000, 64, 48, True)
+
+
+def test_pinhole_exact_with_host_rays(tr):
+    camera_rays_equal_the_oracle_rays(tr, 7, 4000, 64, 48, False)
 
 
 def test_axis_parallel_rays_with_signed_zero_directions(tr):

@@ -333,11 +333,8 @@ def test_spatial_splits_are_pure_acceleration_structure(fisheye):
     assert cnts[(8, 0)]["node_visits"] + cnts[(8, 0)]["proxy_tests"] < cnts[(0, 0)]["node_visits"] + cnts[(0, 0)]["proxy_tests"]
     sc = O.Scene(acts_to_particles(acts))
     ref_u8, ref_f32, rc = sc.render(to_oracle_params(p), threads=8)
-    if fisheye:
-        compare(f32, ref_f32, u8, ref_u8, max_outlier_frac=2e-4, max_outlier=0.08)
-    else:
-        compare(f32, ref_f32, u8, ref_u8)
-        assert rc["hit_evals"] == cnts[(0, 0)]["hit_evals"]
+    compare(f32, ref_f32, u8, ref_u8)
+    assert rc["hit_evals"] == cnts[(0, 0)]["hit_evals"]
     sc.close()
 
 
