@@ -82,12 +82,21 @@ __global__ void k_proxy_boxes(const float* __restrict__ pos, const float* __rest
         r2 = fmaxf(r2, q2);
     }
     float emax = 0.0f;
+    bool finite = true;
 #pragma unroll
     for (int r = 0; r < 3; r++) {
         const float e = 1e-5f * (1.0f + fmaxf(fabsf(l[r]), fabsf(h[r])));
         l[r] -= e;
         h[r] += e;
         emax = fmaxf(emax, e);
+        finite = finite && fabsf(l[r]) < INFINITY && fabsf(h[r]) < INFINITY;
+    }
+    // a NaN or infinite position, scale or rotation: the oracle's exact test never reports such a particle, and a box with one
+    // finite axis would pass the builder's validity test (lo.x <= hi.x) and carry NaN into the scene bounds and every Morton key
+    if (!finite) {
+        lo[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+        hi[i] = make_float4(-1.0f, -1.0f, -1.0f, 0.0f);
+        return;
     }
     // hi.w: radius of a sphere about the BOX CENTRE that holds the proxy (the vertices come in +- pairs, so the box centre is
     // the particle's position up to the rounding the box margin e covers many times over): what the tile kernel's leaf step
@@ -123,7 +132,7 @@ __device__ __forceinline__ PieceGrid piece_grid(const float* __restrict__ scale,
                                                 float tau, float4 lo, float4 hi, float volf)
 {
     PieceGrid g{{1u, 1u, 1u}};
-    if (!(s > 0.0f) || !(tau > 0.0f)) return g;
+    if (!(s > 0.0f) || !(tau > 0.0f) || !(lo.x <= hi.x)) return g; // (an unhittable proxy stays one inverted box)
     const float e[3] = {scale[i * 3] * s * kIcoTT, scale[i * 3 + 1] * s * kIcoTT, scale[i * 3 + 2] * s * kIcoTT};
     const float emin = fminf(e[0], fminf(e[1], e[2])), emax = fmaxf(e[0], fmaxf(e[1], e[2]));
     if (!(2.0f * emax > tau)) return g;
@@ -1053,6 +1062,48 @@ int grt_debug_bvh_depth(grt_ctx* c, uint32_t* out_depth)
         memcpy(&ch[1], &h[(size_t)i * 4 + 3].y, 4);
         for (int k = 0; k < 2; k++)
             if (!(ch[k] & kLeafBit)) stack.emplace_back(ch[k], d + 1u);
+    }
+    return GRT_OK;
+}
+
+// (testing) Copy of a built tree as it lies in device memory, for tests/bvh_check.py; never on a render path.
+int grt_debug_copy_tree(grt_ctx* c, int which, grt_debug_tree* o)
+{
+    if (!c || !o || (which != 0 && which != 1)) return GRT_ERR_INVALID;
+    grt_ctx* sc = scene_of(c);
+    if (which == 0 && !sc->built) { c->err = "grt_debug_copy_tree: no Gaussian BVH has been built"; return GRT_ERR_INVALID; }
+    const DevBvh& b = which == 0 ? sc->gbvh : sc->mbvh;
+    const uint32_t m = (which == 1 && sc->n_faces == 0) ? 0u : b.n_prims;
+    const uint32_t n_nodes = (m > 0 && !(b.root_ref & kLeafBit) && b.nodes) ? m - 1u : 0u;
+    const uint32_t rec_floats = which == 0 ? 16u : 12u;
+    const float4* rec = which == 0 ? sc->d_rec : sc->d_tri;
+    o->n_prims = m;
+    o->n_nodes = n_nodes;
+    o->height = m ? b.height : 0u;
+    o->root_ref = m ? b.root_ref : kNoRoot;
+    o->leaf_max = b.leaf_max;
+    o->has_pieces = (which == 0 && sc->has_pieces) ? 1u : 0u;
+    o->n_qnodes = (which == 0 && b.qnodes) ? n_nodes : 0u;
+    o->n_pbox = (which == 0 && b.pbox) ? m : 0u;
+    o->wide = kTileWide;
+    o->rec_floats = rec_floats;
+    (void)hipSetDevice(sc->device);
+    if (hipDeviceSynchronize() != hipSuccess) { c->err = "grt_debug_copy_tree: hipDeviceSynchronize failed"; return GRT_ERR_HIP; }
+    struct Part { void* dst; const void* src; size_t bytes; };
+    const Part parts[] = {
+        {o->nodes, b.nodes, (size_t)n_nodes * 4 * sizeof(float4)},
+        {o->wnodes, b.wnodes, (size_t)n_nodes * 8 * sizeof(float4)},
+        {o->qnodes, b.qnodes, (size_t)o->n_qnodes * 2 * kTileWide * sizeof(float4)},
+        {o->pbox, b.pbox, (size_t)o->n_pbox * 2 * sizeof(float4)},
+        {o->order, b.order, (size_t)m * sizeof(uint32_t)},
+        {o->rec, rec, (size_t)m * rec_floats * sizeof(float)},
+    };
+    for (const Part& p : parts) {
+        if (!p.dst || !p.bytes) continue;
+        if (!p.src || hipMemcpy(p.dst, p.src, p.bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+            c->err = "grt_debug_copy_tree: copy of the tree failed";
+            return GRT_ERR_HIP;
+        }
     }
     return GRT_OK;
 }

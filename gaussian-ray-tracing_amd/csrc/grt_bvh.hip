@@ -1283,6 +1283,7 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
     out->root_ref = kNoRoot;
     if (n_in == 0) return GRT_OK;
     leaf_max = std::max(1u, std::min(leaf_max, kLeafMaxPrims));
+    out->leaf_max = leaf_max;
     if (n_in > kLeafIndexMask) {
         if (err) *err = "build_lbvh: more than 2^28 primitives";
         return GRT_ERR_LIMIT;

@@ -43,6 +43,7 @@ struct DevBvh {
     uint32_t n_prims = 0;      // valid primitives (leaves)
     uint32_t height = 0;       // levels of internal nodes (bounds the traversal stack)
     uint32_t root_ref = kNoRoot;
+    uint32_t leaf_max = 0;     // primitives per leaf range the build collapsed to (grt_debug_copy_tree)
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     size_t cap_nodes = 0, cap_order = 0;
 };

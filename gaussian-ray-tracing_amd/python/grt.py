@@ -41,6 +41,12 @@ class BvhInfo(C.Structure):
                 ("n_primitives", C.c_uint64)]
 
 
+class DebugTree(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_prims", "n_nodes", "height", "root_ref", "leaf_max", "has_pieces", "n_qnodes",
+                                          "n_pbox", "wide", "rec_floats")] + \
+               [(n, C.c_void_p) for n in ("nodes", "wnodes", "qnodes", "pbox", "order", "rec")]
+
+
 class MemoryInfo(C.Structure):
     _fields_ = [("scene_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("overflow_pool_bytes", C.c_uint64),
                 ("overflow_chunks", C.c_uint32), ("overflow_demand", C.c_uint32)]
@@ -76,7 +82,7 @@ KERNEL_AUTO, KERNEL_PERLANE, KERNEL_WAVE, KERNEL_STREAM, KERNEL_STREAM_BIG, KERN
 
 EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
-    "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_sync",
+    "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -115,6 +121,7 @@ def lib():
         L.grt_update_meshes.argtypes = [vp, C.POINTER(Mesh), u32]
         L.grt_get_bvh_info.argtypes = [vp, C.POINTER(BvhInfo)]
         L.grt_debug_bvh_depth.argtypes = [vp, C.POINTER(u32)]
+        L.grt_debug_copy_tree.argtypes = [vp, C.c_int, C.POINTER(DebugTree)]
         L.grt_render.argtypes = [vp, C.POINTER(Params), vp, vp, u32, u32, u32, u32, vp]
         L.grt_render_tiles.argtypes = [vp, C.POINTER(Params), vp, vp, u32, u32, u32, u32, u32, vp]
         L.grt_assemble_tiles.argtypes = [vp, vp, u32, u32, u32, u32, u32, u32, vp, vp]
@@ -363,6 +370,23 @@ class Tracer:
         d = C.c_uint32(0)
         self._check(lib().grt_debug_bvh_depth(self._h, C.byref(d)))
         return int(d.value)
+
+    def debug_tree(self, which=0):
+        """(testing) copy of the built Gaussian (which = 0) or mesh (1) tree as numpy arrays: nodes [n][16] float32, wnodes [n][32],
+        qnodes [n][wide][8], pbox [m][8], order [m] uint32, rec [m][16] (Gaussian) / [m][12] (mesh) and the counts as ints.  Child refs and ids are the
+        raw bits of floats: .view(np.uint32) reads them."""
+        t = DebugTree()
+        self._check(lib().grt_debug_copy_tree(self._h, which, C.byref(t)))
+        w = t.wide
+        out = {n: int(getattr(t, n)) for n in ("n_prims", "n_nodes", "height", "root_ref", "leaf_max", "has_pieces", "wide")}
+        arr = {"nodes": np.zeros((t.n_nodes, 16), np.float32), "wnodes": np.zeros((t.n_nodes, 32), np.float32),
+               "qnodes": np.zeros((t.n_qnodes, w, 8), np.float32), "pbox": np.zeros((t.n_pbox, 8), np.float32),
+               "order": np.zeros(t.n_prims, np.uint32), "rec": np.zeros((t.n_prims, t.rec_floats), np.float32)}
+        for n, a in arr.items():
+            setattr(t, n, a.ctypes.data if a.size else None)
+        self._check(lib().grt_debug_copy_tree(self._h, which, C.byref(t)))
+        out.update(arr)
+        return out
 
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)

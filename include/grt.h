@@ -267,6 +267,21 @@ GRT_API int grt_get_memory_info(const grt_ctx* ctx, grt_memory_info* out);
 /* (testing) depth of the Gaussian LBVH walked on the host over a copy of its node records, in levels of internal nodes: must not
  * exceed grt_bvh_info::height, which sizes the kernels' traversal stacks (synchronises the device; ~0.1 s per million nodes). */
 GRT_API int grt_debug_bvh_depth(grt_ctx* ctx, uint32_t* out_depth);
+/* (testing) A copy of a built tree, for checkers that restate its invariants (tests/bvh_check.py).  Two calls: with every buffer
+ * NULL the counts are filled in; then every non-NULL buffer receives its array (sized by those counts).  Synchronises the device.
+ * which = 0: the Gaussian LBVH, rec = the proxy records [n_prims][16]; which = 1: the mesh LBVH, rec = the triangles [n_prims][12].
+ * n_nodes = 0 when the root is a leaf range; qnodes and pbox exist for the Gaussian tree only (n_qnodes = n_pbox = 0 otherwise). */
+typedef struct {
+    uint32_t n_prims, n_nodes, height, root_ref, leaf_max, has_pieces;
+    uint32_t n_qnodes, n_pbox, wide, rec_floats; /* wide = children per qnodes record; rec_floats = floats per record (16 or 12) */
+    float* nodes;     /* [n_nodes][16]: the binary records, child refs as raw bits in floats 12, 13 */
+    float* wnodes;    /* [n_nodes][32]: the 4-wide records */
+    float* qnodes;    /* [n_qnodes][wide][8]: the per-child records of the tile kernel */
+    float* pbox;      /* [n_pbox][8]: (lo.xyz, 0)(hi.xyz, radius) of every sorted primitive */
+    uint32_t* order;  /* [n_prims]: sorted position -> input primitive (piece, particle or face) */
+    float* rec;       /* [n_prims][rec_floats] */
+} grt_debug_tree;
+GRT_API int grt_debug_copy_tree(grt_ctx* ctx, int which, grt_debug_tree* out);
 
 /* ---- render (all asynchronous on `stream`, a hipStream_t; NULL = the context's own stream) ----
  * d_rgb8 : device uchar3 frame, row-major y*width+x (shaders/tracer.cuh:484-496), may be NULL

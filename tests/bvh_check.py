@@ -1,0 +1,767 @@
+"""Float64 checker of the trees the library builds on the device (grt_debug_copy_tree, grt.Tracer.debug_tree).
+
+It restates the layouts from their documented encodings (include/grt.h, csrc/grt_internal.h DevBvh) and shares no code with
+csrc/.  Every invariant the kernels and the oracle comparison rest on is checked:
+
+  G1 primitive set     every hittable particle (or every cell of a split one) exactly once; nothing else
+  G2 topology          a tree from root_ref, leaf ranges of 1..leaf_max that partition [0, n_prims), depth <= height
+  G3 containment       the box a node holds for a child EQUALS the union of what that child holds (bit for bit: the builder
+                       forms unions with fminf / fmaxf, anything else is a stale or corrupted record)
+  G4 geometry          primitive boxes strictly contain their proxy (icosahedron) / cell / triangle, in float64
+  G5 piece ownership   every event of a split particle is owned by exactly one piece, whose box holds the event's point
+  G6 records           the per-primitive records equal the oracle's values bit for bit
+  G7 wide layouts      wnodes / qnodes restate the binary tree; the qnodes walk reaches every primitive once; the wide height
+                       the tile kernel's stack is sized by
+
+check_gaussian_tree / check_mesh_tree raise one AssertionError listing every violation found (tagged G1..G7, naming the node,
+slot, primitive or particle) and otherwise return a report of what was measured.
+"""
+import ctypes as C
+
+import numpy as np
+
+LEAF_BIT = 0x80000000
+LEAF_INDEX_MASK = 0x0FFFFFFF
+NO_ROOT = 0xFFFFFFFF
+TILE_STACK = 288          # entries of the tile kernel's depth-first stack
+ICO_TT_F32 = np.float32(1.0704663)  # the icosahedron's extent along its principal axes, as the kernels hold it
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# encodings
+# ---------------------------------------------------------------------------------------------------------------------
+def u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def is_leaf(ref):
+    return (np.asarray(ref, np.uint32) & LEAF_BIT) != 0
+
+
+def leaf_first(ref):
+    return np.asarray(ref, np.uint32) & LEAF_INDEX_MASK
+
+
+def leaf_count(ref):
+    return ((np.asarray(ref, np.uint32) >> 28) & 7) + 1
+
+
+def node_boxes(nodes):
+    """binary records [n][16] -> child boxes [n][2][6] (lo.xyz hi.xyz) and refs [n][2]"""
+    b = np.stack([nodes[:, 0:6], nodes[:, 6:12]], axis=1)
+    return b, u32(nodes[:, 12:14])
+
+
+def wnode_boxes(wn):
+    """4-wide records [n][32]: per child (lo.x lo.y hi.x hi.y lo.z hi.z) -> [n][4][6] (lo.xyz hi.xyz), refs [n][4]"""
+    c = wn[:, :24].reshape(-1, 4, 6)
+    return c[:, :, [0, 1, 4, 2, 3, 5]], u32(wn[:, 24:28])
+
+
+def qnode_boxes(qn):
+    """per-child records [n][W][8] = (lo.xyz ref)(hi.xyz w) -> [n][W][6], refs [n][W]"""
+    return np.concatenate([qn[:, :, 0:3], qn[:, :, 4:7]], axis=2), u32(qn[:, :, 3])
+
+
+def tt_constants():
+    rr = (3.0 + np.sqrt(5.0)) / (2.0 * np.sqrt(3.0))
+    return 1.0 / rr, (1.0 + np.sqrt(5.0)) / (2.0 * rr)
+
+
+def icosahedron64():
+    ss, tt = tt_constants()
+    return np.array([[-ss, tt, 0], [ss, tt, 0], [-ss, -tt, 0], [ss, -tt, 0], [0, -ss, tt], [0, ss, tt],
+                     [0, -ss, -tt], [0, ss, -tt], [tt, 0, -ss], [tt, 0, ss], [-tt, 0, -ss], [-tt, 0, ss]], np.float64)
+
+
+def rot64(quat):
+    """glm::mat3_cast of (w x y z) in float64: R[n][3][3] with R @ v mapping principal to world coordinates"""
+    q = np.asarray(quat, np.float64)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.empty((len(q), 3, 3))
+    # columns of the rotation (Rg column-major: Rg[c*3 + r] = R[r][c])
+    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 1, 0] = 2 * (x * y + w * z); R[:, 2, 0] = 2 * (x * z - w * y)
+    R[:, 0, 1] = 2 * (x * y - w * z); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 2, 1] = 2 * (y * z + w * x)
+    R[:, 0, 2] = 2 * (x * z + w * y); R[:, 1, 2] = 2 * (y * z - w * x); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
+    return R
+
+
+def rg32(quat):
+    """mat3_cast in float32 with the kernels' operation order: Rg[n][9], column-major"""
+    q = np.asarray(quat, np.float32)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    one, two = np.float32(1), np.float32(2)
+    qxx, qyy, qzz = x * x, y * y, z * z
+    qxz, qxy, qyz = x * z, x * y, y * z
+    qwx, qwy, qwz = w * x, w * y, w * z
+    return np.stack([one - two * (qyy + qzz), two * (qxy + qwz), two * (qxz - qwy),
+                     two * (qxy - qwz), one - two * (qxx + qzz), two * (qyz + qwx),
+                     two * (qxz + qwy), two * (qyz - qwx), one - two * (qxx + qyy)], axis=1)
+
+
+def inv_cov32(quat, scale):
+    """A[n][9] row-major = (1/scale_r) * Rg[r*3 + c] in float32 (grto_inv_cov)"""
+    Rg = rg32(quat)
+    inv = np.float32(1) / np.asarray(scale, np.float32)
+    return (np.repeat(inv, 3, axis=1) * Rg).astype(np.float32)
+
+
+def hittable(particles, alpha_min):
+    """s = sqrtf(2 logf(opacity / alpha_min)) > 0, i.e. opacity / alpha_min > 1 in float32, and every attribute finite"""
+    op = np.asarray(particles["opacity"], np.float32)
+    ratio = op / np.float32(alpha_min)
+    fin = np.isfinite(particles["pos"]).all(1) & np.isfinite(particles["scale"]).all(1) & np.isfinite(particles["quat"]).all(1)
+    with np.errstate(invalid="ignore"):
+        return (ratio > 1) & fin
+
+
+def proxy_scale(opacity, alpha_min):
+    """grto_proxy_scale of the oracle (the host libm the library also uses), one value per particle"""
+    import oracle as O
+    L = O.lib()
+    return np.array([L.grto_proxy_scale(float(o), float(alpha_min)) for o in np.asarray(opacity, np.float32)], np.float32)
+
+
+def desc_cells(desc):
+    """cell descriptor -> (k[n][3], p[n][3])"""
+    d = np.asarray(desc, np.uint32)
+    k = np.stack([(d >> (10 * r)) & 31 for r in range(3)], 1).astype(np.int64)
+    p = np.stack([((d >> (10 * r + 5)) & 31) + 1 for r in range(3)], 1).astype(np.int64)
+    return k, p
+
+
+def piece_owner_cells(desc, s, o_g, d_g, t):
+    """numpy-float32 restatement of piece_owns (grt_device.h): the cell index of o_g + t d_g along each principal axis, with the
+    kernel's operation order.  Returns (cell[n][3] int, candidate sets per axis as [n][3][2] = lowest/highest index reached under
+    +-2 ulp of y)."""
+    _, p = desc_cells(desc)
+    s = np.asarray(s, np.float32)
+    inv = np.float32(0.5) / (ICO_TT_F32 * s)
+    t = np.asarray(t, np.float32)[:, None]
+    y = (o_g + t * d_g).astype(np.float32)
+    fp = p.astype(np.float32)
+
+    def cell(yy):
+        c = np.floor((yy * inv[:, None] + np.float32(0.5)) * fp).astype(np.float32)
+        return np.minimum(np.maximum(c, 0), fp - 1).astype(np.int64)
+
+    y_lo = np.nextafter(np.nextafter(y, -np.inf), -np.inf)
+    y_hi = np.nextafter(np.nextafter(y, np.inf), np.inf)
+    return cell(y), np.stack([cell(y_lo), cell(y_hi)], axis=2)
+
+
+class Report(dict):
+    pass
+
+
+class _Faults:
+    def __init__(self, limit=6):
+        self.items = {}
+        self.limit = limit
+
+    def add(self, tag, msg):
+        self.items.setdefault(tag, []).append(msg)
+
+    def check(self, tag, ok, fmt):
+        """ok: boolean array; fmt(i) names the i-th failing element"""
+        bad = np.flatnonzero(~np.asarray(ok, bool).ravel())
+        for i in bad[:self.limit]:
+            self.add(tag, fmt(int(i)))
+        if len(bad) > self.limit:
+            self.add(tag, f"... and {len(bad) - self.limit} more")
+        return len(bad) == 0
+
+    def raise_if_any(self, what):
+        if self.items:
+            lines = [f"{what}: the tree violates {len(self.items)} invariant(s):"]
+            for tag in sorted(self.items):
+                lines += [f"  {tag}: {m}" for m in self.items[tag]]
+            raise AssertionError("\n".join(lines))
+
+
+def _eq6(a, b):
+    """exact equality of boxes (value equality of float32: a one-ulp difference fails, +0 == -0)"""
+    return (np.asarray(a, np.float32) == np.asarray(b, np.float32)).all(-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# G2 + G3: the binary tree
+# ---------------------------------------------------------------------------------------------------------------------
+def _walk_binary(dump, F, prim_lo, prim_hi):
+    """G2 + G3.  prim_lo / prim_hi [m][3]: the boxes a leaf range is the union of.  Returns (reachable nodes in walk order,
+    their depths, signatures per node (count, sum, sum of squares of primitive positions), box held for each ref)."""
+    m, n_nodes, root = dump["n_prims"], dump["n_nodes"], dump["root_ref"]
+    leaf_max, height = dump["leaf_max"], dump["height"]
+    info = {"walked_depth": 0}
+    if m == 0:
+        F.check("G2", [root == NO_ROOT and n_nodes == 0], lambda i: f"empty tree with root_ref {root:#x} and {n_nodes} nodes")
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), info
+    if m <= leaf_max:
+        want = LEAF_BIT | ((m - 1) << 28)
+        F.check("G2", [root == want and n_nodes == 0],
+                lambda i: f"{m} primitives <= leaf_max {leaf_max}: root_ref {root:#x} (want the leaf range {want:#x}) and {n_nodes} nodes (want 0)")
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), info
+    if not F.check("G2", [not (root & LEAF_BIT) and root < n_nodes], lambda i: f"root_ref {root:#x} is not an internal node"):
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), info
+    boxes, refs = node_boxes(dump["nodes"])
+    visits = np.zeros(n_nodes, np.int64)
+    order, depth = [], []
+    frontier = np.array([root], np.int64)
+    d = 1
+    while len(frontier):
+        np.add.at(visits, frontier, 1)
+        again = visits[frontier] > 1
+        if again.any():
+            F.check("G2", ~again, lambda i: f"node {frontier[i]} reached more than once (a cycle or a shared child), at depth {d}")
+            frontier = frontier[~again]
+            frontier = np.unique(frontier[visits[frontier] == 1])
+            if not len(frontier):
+                break
+        order.append(frontier)
+        depth.append(np.full(len(frontier), d))
+        r = refs[frontier].ravel()
+        internal = r[~is_leaf(r)].astype(np.int64)
+        out = internal >= n_nodes
+        if out.any():
+            F.check("G2", ~out, lambda i: f"child ref {internal[i]:#x} points past the {n_nodes} node records")
+            internal = internal[~out]
+        frontier = internal
+        d += 1
+        if d > n_nodes + 2:
+            F.add("G2", "the walk does not end")
+            break
+    order = np.concatenate(order) if order else np.zeros(0, np.int64)
+    depth = np.concatenate(depth) if depth else np.zeros(0, np.int64)
+    info["walked_depth"] = int(depth.max()) if len(depth) else 0
+    F.check("G2", [info["walked_depth"] <= height],
+            lambda i: f"walked depth {info['walked_depth']} exceeds the reported height {height} (the traversal stacks are sized by it)")
+    # leaf ranges
+    r = refs[order]                      # [k][2]
+    lr = r[is_leaf(r)]
+    first, cnt = leaf_first(lr).astype(np.int64), leaf_count(lr).astype(np.int64)
+    F.check("G2", cnt <= leaf_max, lambda i: f"leaf range {lr[i]:#x} holds {cnt[i]} primitives > leaf_max {leaf_max}")
+    F.check("G2", first + cnt <= m, lambda i: f"leaf range {lr[i]:#x} reaches past the {m} primitives")
+    cover = np.zeros(m + 8, np.int64)
+    for c in range(1, 9):
+        sel = cnt == c
+        for k in range(c):
+            np.add.at(cover, np.minimum(first[sel] + k, m + 7), 1)
+    cover = cover[:m]
+    F.check("G2", cover >= 1, lambda i: f"primitive {i} is in no leaf range (dropped)")
+    F.check("G2", cover <= 1, lambda i: f"primitive {i} is in {cover[i]} leaf ranges (duplicated)")
+    # G3: boxes held for internal children equal the union of the two boxes the child holds; leaf ranges the union of
+    # their primitives' boxes
+    kids = r.ravel()
+    held = boxes[order].reshape(-1, 6)
+    par = np.repeat(order, 2)
+    slot = np.tile([0, 1], len(order))
+    inn = ~is_leaf(kids) & (kids < n_nodes)
+    ci = kids[inn].astype(np.int64)
+    cb = boxes[ci]
+    uni = np.concatenate([np.minimum(cb[:, 0, :3], cb[:, 1, :3]), np.maximum(cb[:, 0, 3:], cb[:, 1, 3:])], 1)
+    ok = _eq6(held[inn], uni)
+    pi, si = par[inn], slot[inn]
+    F.check("G3", ok, lambda i: f"node {pi[i]} child {si[i]} (node {ci[i]}): held box {held[inn][i].tolist()} != union of its children "
+                                f"{uni[i].tolist()}")
+    lf = is_leaf(kids)
+    fl, cl = leaf_first(kids[lf]).astype(np.int64), leaf_count(kids[lf]).astype(np.int64)
+    fl, cl = np.minimum(fl, m - 1), np.minimum(cl, m - np.minimum(fl, m - 1))
+    ulo = np.full((len(fl), 3), np.inf, np.float32)
+    uhi = np.full((len(fl), 3), -np.inf, np.float32)
+    for k in range(int(cl.max()) if len(cl) else 0):
+        sel = cl > k
+        ulo[sel] = np.minimum(ulo[sel], prim_lo[fl[sel] + k])
+        uhi[sel] = np.maximum(uhi[sel], prim_hi[fl[sel] + k])
+    uni = np.concatenate([ulo, uhi], 1)
+    ok = _eq6(held[lf], uni)
+    pl, sl = par[lf], slot[lf]
+    F.check("G3", ok, lambda i: f"node {pl[i]} child {sl[i]} (leaf range first {fl[i]} count {cl[i]}): held box {held[lf][i].tolist()} "
+                                f"!= union of its primitives' boxes {uni[i].tolist()}")
+    return order, depth, info
+
+
+def _ref_sig(r, sig, n_nodes):
+    """(count, sum, sum of squares) of the sorted positions below each ref: arithmetic for a leaf range, sig[] for a node"""
+    r = np.asarray(r, np.uint32)
+    out = np.zeros(r.shape + (3,), np.int64)          # exact: sums of squares of 2^28 positions stay below 2^63
+    lf = is_leaf(r)
+    f, c = leaf_first(r[lf]).astype(np.int64), leaf_count(r[lf]).astype(np.int64)
+    out[lf, 0] = c
+    out[lf, 1] = c * f + c * (c - 1) // 2
+    out[lf, 2] = c * f * f + f * c * (c - 1) + (c - 1) * c * (2 * c - 1) // 6
+    ii = (~lf) & (r < n_nodes)
+    out[ii] = sig[r[ii].astype(np.int64)]
+    return out
+
+
+def _signatures(dump, order, depth):
+    """per reachable node: the signature of its primitives, bottom-up by walked depth"""
+    n_nodes = dump["n_nodes"]
+    _, refs = node_boxes(dump["nodes"])
+    sig = np.zeros((n_nodes, 3), np.int64)
+    for d in range(int(depth.max()), 0, -1):
+        at = order[depth == d]
+        sig[at] = _ref_sig(refs[at], sig, n_nodes).sum(1)
+    return sig
+
+
+def _check_wide(dump, order, depth, F, rep):
+    """G7: wnodes and qnodes against the binary tree"""
+    n_nodes, m, root, W = dump["n_nodes"], dump["n_prims"], dump["root_ref"], dump["wide"]
+    rep["wide_height"] = 0
+    if n_nodes == 0 or not len(order):
+        return
+    boxes, refs = node_boxes(dump["nodes"])
+    inv_box = np.array([1, 1, 1, -1, -1, -1], np.float32)
+    # wnodes: exactly the grandchildren the k_widen rule gives (a leaf child stays as it is), then unused slots
+    k = len(order)
+    eb = np.tile(inv_box, (k, 4, 1))
+    er = np.full((k, 4), NO_ROOT, np.uint32)
+    pos = np.zeros(k, np.int64)
+    ar = np.arange(k)
+    for c in range(2):
+        r = refs[order, c]
+        lf = is_leaf(r) | (r >= n_nodes)
+        ci = np.where(lf, 0, r).astype(np.int64)
+        eb[ar[lf], pos[lf]] = boxes[order[lf], c]
+        er[ar[lf], pos[lf]] = r[lf]
+        nl = ~lf
+        for g in range(2):
+            eb[ar[nl], pos[nl] + g] = boxes[ci[nl], g]
+            er[ar[nl], pos[nl] + g] = refs[ci[nl], g]
+        pos += np.where(lf, 1, 2)
+    wb, wr = wnode_boxes(dump["wnodes"])
+    ok = (wr[order] == er) & _eq6(wb[order], eb)
+    bad = np.argwhere(~ok)
+    for i, sl in bad[:6]:
+        F.add("G7", f"wnodes[{order[i]}] slot {sl}: ref {int(wr[order[i], sl]):#x} box {wb[order[i], sl].tolist()}, the binary tree "
+                    f"gives ref {int(er[i, sl]):#x} box {eb[i, sl].tolist()}")
+    if len(bad) > 6:
+        F.add("G7", f"... and {len(bad) - 6} more wnodes slots")
+    if dump.get("qnodes") is None or len(dump["qnodes"]) == 0:
+        rep["wide_height"] = None
+        return
+    qb, qr = qnode_boxes(dump["qnodes"])
+    # the box the binary tree holds for every ref: by node index for internal refs, by first primitive for leaf ranges
+    held_int = np.full((n_nodes, 6), np.nan, np.float32)
+    held_leaf = np.full((m, 6), np.nan, np.float32)
+    leaf_ref = np.full(m, NO_ROOT, np.uint32)
+    r = refs[order].ravel()
+    hb = boxes[order].reshape(-1, 6)
+    lf = is_leaf(r)
+    held_int[r[~lf & (r < n_nodes)].astype(np.int64)] = hb[~lf & (r < n_nodes)]
+    fl = np.minimum(leaf_first(r[lf]), m - 1).astype(np.int64)
+    held_leaf[fl] = hb[lf]
+    leaf_ref[fl] = r[lf]
+    reach = np.zeros(n_nodes, bool)
+    reach[order] = True
+    sig = _signatures(dump, order, depth)
+    q = qr[order]                                        # [k][W]
+    qbox = qb[order]
+    used = q != NO_ROOT
+    bad = np.argwhere(~used & ~_eq6(qbox, inv_box))
+    for i, sl in bad[:6]:
+        F.add("G7", f"qnodes[{order[i]}] slot {sl}: unused (kNoRoot) but its box {qbox[i, sl].tolist()} is not the inverted box")
+    lf = is_leaf(q) & used
+    inn = ~is_leaf(q) & used
+    bad_int = inn & ((q >= n_nodes) | ~reach[np.minimum(q, n_nodes - 1).astype(np.int64)])
+    qf = np.minimum(leaf_first(q), m - 1).astype(np.int64)
+    bad_leaf = lf & (leaf_ref[qf] != q)
+    for i, sl in np.argwhere(bad_int | bad_leaf)[:6]:
+        F.add("G7", f"qnodes[{order[i]}] slot {sl}: ref {int(q[i, sl]):#x} is no node or leaf range of the tree")
+    want = np.where(lf[..., None], held_leaf[qf], held_int[np.minimum(q, n_nodes - 1).astype(np.int64)])
+    okb = ~used | bad_int | bad_leaf | _eq6(qbox, want)
+    for i, sl in np.argwhere(~okb)[:6]:
+        F.add("G7", f"qnodes[{order[i]}] slot {sl} (ref {int(q[i, sl]):#x}): box {qbox[i, sl].tolist()} != the box the binary tree holds "
+                    f"for it {want[i, sl].tolist()}")
+    got = np.where(used[..., None], _ref_sig(np.where(used, q, 0), sig, n_nodes), 0).sum(1)
+    oks = (got == sig[order]).all(1)
+    F.check("G7", oks, lambda i: f"qnodes[{order[i]}]: its slots cover (count, sum, sum of squares) {got[i].tolist()} of the primitives, "
+                                 f"node {order[i]} holds {sig[order[i]].tolist()}")
+    # the walk through qnodes alone: every primitive exactly once; the wide height
+    cover = np.zeros(m + 8, np.int64)
+    frontier = np.array([root], np.int64)
+    seen = np.zeros(n_nodes, np.int64)
+    wh = 0
+    while len(frontier) and wh <= n_nodes:
+        wh += 1
+        np.add.at(seen, frontier, 1)
+        r = qr[frontier].ravel()
+        r = r[r != NO_ROOT]
+        lf = is_leaf(r)
+        f, c = leaf_first(r[lf]).astype(np.int64), leaf_count(r[lf]).astype(np.int64)
+        for kk in range(8):
+            sel = c > kk
+            np.add.at(cover, np.minimum(f[sel] + kk, m + 7), 1)
+        nxt = r[~lf].astype(np.int64)
+        nxt = nxt[nxt < n_nodes]
+        frontier = nxt[seen[nxt] == 0]
+    cover = cover[:m]
+    F.check("G7", cover >= 1, lambda i: f"the walk through qnodes never reaches primitive {i}")
+    F.check("G7", cover <= 1, lambda i: f"the walk through qnodes reaches primitive {i} {cover[i]} times")
+    rep["wide_height"] = wh
+    h = dump["height"]
+    bound = (h + 2) // 3
+    rep["wide_bound"] = bound
+    admitted = bound * (W - 1) + 64 <= TILE_STACK
+    rep["tile_admitted"] = bool(admitted)
+    # the tile kernel's stack takes up to W - 1 siblings per wide level below the overflowing batch of <= 64
+    if admitted:
+        F.check("G7", [wh <= bound],
+                lambda i: f"stack premise: {wh} wide levels on a path through qnodes, the tile kernel admits the tree by (height {h} + 2) / 3 "
+                          f"= {bound} and holds {(TILE_STACK - 64) // (W - 1)}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Gaussian tree
+# ---------------------------------------------------------------------------------------------------------------------
+def check_gaussian_tree(dump, particles, alpha_min=0.01, n_primitives=None, g5_particles=2000, g5_rays=12, sample=None, seed=0):
+    """dump: Tracer.debug_tree(0) (or the same arrays from the fixture); particles: dict pos [n][3], scale [n][3], quat [n][4]
+    (w x y z), opacity [n] as uploaded.  sample: check G4 / G6 on this many primitives only (None = all).  Returns the report."""
+    F = _Faults()
+    rep = Report()
+    m = dump["n_prims"]
+    pos = np.asarray(particles["pos"], np.float32)
+    scale = np.asarray(particles["scale"], np.float32)
+    quat = np.asarray(particles["quat"], np.float32)
+    opac = np.asarray(particles["opacity"], np.float32)
+    n = len(pos)
+    rec = np.asarray(dump["rec"], np.float32)
+    pbox = np.asarray(dump["pbox"], np.float32)
+    order = np.asarray(dump["order"], np.uint32)
+    ids = u32(rec[:, 11]).astype(np.int64) if m else np.zeros(0, np.int64)
+    desc = u32(rec[:, 15]) if m else np.zeros(0, np.uint32)
+    rep["n_prims"] = m
+    # ---- G1 ----
+    if n_primitives is not None:
+        F.check("G1", [m == n_primitives], lambda i: f"n_prims {m} != bvh_info n_primitives {n_primitives}")
+    F.check("G1", [len(np.unique(order)) == len(order)], lambda i: "order repeats an index")
+    F.check("G1", ids < n, lambda i: f"record {i} names particle {ids[i]}, past the {n} uploaded")
+    ids_c = np.minimum(ids, max(n - 1, 0))
+    hit = hittable(particles, alpha_min) if n else np.zeros(0, bool)
+    F.check("G1", hit[ids_c] if n else np.ones(0, bool),
+            lambda i: f"record {i} names particle {ids[i]}, which is not hittable (opacity {opac[ids_c[i]]} vs alpha_min, or a non-finite value)")
+    whole = desc == 0
+    cnt_whole = np.bincount(ids_c[whole], minlength=n) if n else np.zeros(0, np.int64)
+    split_ids = np.unique(ids_c[~whole])
+    present = np.bincount(ids_c, minlength=n) > 0 if n else np.zeros(0, bool)
+    F.check("G1", ~(hit & ~present), lambda i: f"hittable particle {i} is not in the tree")
+    F.check("G1", cnt_whole <= 1, lambda i: f"particle {i} appears {cnt_whole[i]} times as a whole proxy")
+    both = np.zeros(n, bool)
+    both[split_ids] = True
+    F.check("G1", ~(both & (cnt_whole > 0)), lambda i: f"particle {i} is in the tree both whole and as pieces")
+    if (~whole).any():
+        k, p = desc_cells(desc[~whole])
+        top = (desc[~whole] & 0x80000000) != 0
+        jj = np.flatnonzero(~whole)
+        F.check("G1", top, lambda i: f"record {jj[i]}: cell descriptor {desc[jj[i]]:#x} lacks its marker bit")
+        F.check("G1", (k < p).all(1), lambda i: f"record {jj[i]}: cell {k[i].tolist()} outside its grid {p[i].tolist()}")
+        F.check("G1", (p <= 32).all(1) & (p.prod(1) <= 512) & (p.prod(1) > 1),
+                lambda i: f"record {jj[i]}: grid {p[i].tolist()} (per axis <= 32, at most 512 cells, more than one)")
+        sid = ids_c[~whole]
+        o = np.lexsort((k[:, 2], k[:, 1], k[:, 0], sid))
+        sid_o, k_o, p_o = sid[o], k[o], p[o]
+        starts = np.flatnonzero(np.r_[True, sid_o[1:] != sid_o[:-1]])
+        ends = np.r_[starts[1:], len(sid_o)]
+        for a, b in zip(starts, ends):
+            i = int(sid_o[a])
+            pp = p_o[a:b]
+            if not (pp == pp[0]).all():
+                F.add("G1", f"particle {i}: its pieces disagree on the grid ({np.unique(pp, axis=0).tolist()})")
+                continue
+            g = pp[0]
+            lin = k_o[a:b, 0] + g[0] * (k_o[a:b, 1] + g[1] * k_o[a:b, 2])
+            cells = np.bincount(lin, minlength=int(g.prod()))
+            if len(cells) != g.prod() or not (cells == 1).all():
+                miss = np.flatnonzero(cells == 0)[:3].tolist()
+                dup = np.flatnonzero(cells > 1)[:3].tolist()
+                F.add("G1", f"particle {i}: its pieces do not form its {g.tolist()} grid once each (missing cells {miss}, repeated {dup})")
+    rep["n_split_particles"] = int(len(split_ids))
+    # ---- G6: records against the oracle's values ----
+    rng = np.random.default_rng(seed)
+    js = np.arange(m) if sample is None or sample >= m else np.sort(rng.choice(m, sample, replace=False))
+    if len(js):
+        pid = ids_c[js]
+        s_ref = proxy_scale(opac[pid], alpha_min)
+        A_ref = inv_cov32(quat[pid], scale[pid])
+        r = rec[js]
+        got = np.concatenate([r[:, 0:3], r[:, 3:4], r[:, [4, 5, 6, 8, 9, 10, 12, 13, 14]], r[:, 7:8]], 1)
+        want = np.concatenate([pos[pid], s_ref[:, None], A_ref, opac[pid, None]], 1)
+        names = ["mu.x", "mu.y", "mu.z", "s"] + [f"A{a}{b}" for a in range(3) for b in range(3)] + ["opacity"]
+        eq = u32(got) == u32(want)
+        bad = np.flatnonzero(~eq.all(1))
+        for b in bad[:6]:
+            c = int(np.flatnonzero(~eq[b])[0])
+            F.add("G6", f"record {js[b]} (particle {pid[b]}): {names[c]} = {got[b, c]!r} ({u32(got[b:b+1, c])[0]:#010x}), the oracle's "
+                        f"{want[b, c]!r} ({u32(want[b:b+1, c])[0]:#010x})")
+        if len(bad) > 6:
+            F.add("G6", f"... and {len(bad) - 6} more records")
+        # the cell descriptor of a record must be the one of the piece `order` names: pieces of a particle are numbered
+        # k0 + p0 (k1 + p1 k2) from the particle's first piece on, so order - (the particle's first piece) recovers the cell
+        if (~whole).any():
+            j_s = js[~whole[js]]
+            k, p = desc_cells(desc[j_s])
+            lin = k[:, 0] + p[:, 0] * (k[:, 1] + p[:, 1] * k[:, 2])
+            base = order[j_s].astype(np.int64) - lin
+            pidp = ids_c[j_s]
+            # every piece of a particle must point back at the same first piece
+            first_of = {}
+            for jj, b, i in zip(j_s, base, pidp):
+                if first_of.setdefault(int(i), int(b)) != int(b):
+                    F.add("G6", f"record {jj} (particle {i}): cell descriptor {desc[jj]:#x} is not the cell of piece {order[jj]}")
+    # ---- G4: primitive boxes against the geometry, float64 ----
+    lo, hi = pbox[:, 0:3], pbox[:, 4:7]
+    rad = pbox[:, 7]
+    if len(js):
+        V = icosahedron64()
+        pid = ids_c[js]
+        s64 = np.asarray(rec[js, 3], np.float64)
+        R = rot64(quat[pid])
+        S = np.asarray(scale[pid], np.float64) * s64[:, None]
+        verts = np.asarray(pos[pid], np.float64)[:, None, :] + np.einsum("nrc,nvc->nvr", R, V[None, :, :] * S[:, None, :])
+        vlo, vhi = verts.min(1), verts.max(1)
+        wj = whole[js]
+        jw = js[wj]
+        l64, h64 = lo[jw].astype(np.float64), hi[jw].astype(np.float64)
+        okb = (l64 < vlo[wj]).all(1) & (h64 > vhi[wj]).all(1)
+        F.check("G4", okb, lambda i: f"primitive {jw[i]} (particle {ids_c[jw[i]]}): box {lo[jw[i]].tolist()} .. {hi[jw[i]].tolist()} does not "
+                                     f"strictly contain its proxy's vertices {vlo[wj][i].tolist()} .. {vhi[wj][i].tolist()}")
+        cen = 0.5 * (l64 + h64)
+        vr = np.sqrt(((verts[wj] - cen[:, None, :]) ** 2).sum(-1)).max(1)
+        F.check("G4", rad[jw].astype(np.float64) >= vr,
+                lambda i: f"primitive {jw[i]} (particle {ids_c[jw[i]]}): radius hi.w {rad[jw[i]]!r} < the vertices' distance {vr[i]!r} from the box centre")
+        if wj.any():
+            marg = np.minimum(vlo[wj] - l64, h64 - vhi[wj]) / np.maximum(h64 - l64, 1e-30)
+            rep["g4_min_rel_margin_whole"] = float(marg.min())
+        # pieces: inside the whole proxy's box, holding the 8 corners of the cell, radius +inf
+        jp = js[~wj]
+        if len(jp):
+            k, p = desc_cells(desc[jp])
+            _, tt = tt_constants()
+            e = S[~wj] * tt                                      # half extent along each principal axis
+            w = 2 * e / p
+            corners = np.array([[a, b, c] for a in (0, 1) for b in (0, 1) for c in (0, 1)], np.float64)
+            loc = -e[:, None, :] + (k[:, None, :] + corners[None]) * w[:, None, :]   # [n][8][3] principal
+            Rp = R[~wj]
+            wc = np.asarray(pos[ids_c[jp]], np.float64)[:, None, :] + np.einsum("nrc,nvc->nvr", Rp, loc)
+            # the builder clips a cell's box to the whole proxy's box: what the piece must hold is its cell within the proxy, whose
+            # box holds the cell's corners clipped to the proxy's own vertex box
+            vw = verts[~wj]
+            clo, chi = np.maximum(wc.min(1), vw.min(1)), np.minimum(wc.max(1), vw.max(1))
+            pl, ph = lo[jp].astype(np.float64), hi[jp].astype(np.float64)
+            okc = (pl <= clo).all(1) & (ph >= chi).all(1)
+            F.check("G4", okc, lambda i: f"piece {jp[i]} (particle {ids_c[jp[i]]}, cell {k[i].tolist()} of {p[i].tolist()}): box "
+                                         f"{lo[jp[i]].tolist()} .. {hi[jp[i]].tolist()} misses a corner of its cell {clo[i].tolist()} .. {chi[i].tolist()}")
+            inside = (pl >= vw.min(1) - 1e-5 * (1 + np.abs(vw.min(1))) * 4).all(1) & (ph <= vw.max(1) + 1e-5 * (1 + np.abs(vw.max(1))) * 4).all(1)
+            F.check("G4", inside, lambda i: f"piece {jp[i]} (particle {ids_c[jp[i]]}): box reaches outside the whole proxy's box")
+            F.check("G4", np.isposinf(rad[jp]), lambda i: f"piece {jp[i]}: radius {rad[jp[i]]!r}, a piece has none (+inf)")
+    # ---- G2 + G3 ----
+    worder, wdepth, winfo = _walk_binary(dump, F, lo, hi)
+    rep.update(winfo)
+    rep["height"] = dump["height"]
+    # ---- G7 ----
+    _check_wide(dump, worder, wdepth, F, rep)
+    # ---- G5: piece ownership ----
+    if len(split_ids) and g5_particles:
+        _check_pieces(dump, particles, alpha_min, ids_c, desc, lo, hi, split_ids, F, rep, g5_particles, g5_rays, rng)
+    F.raise_if_any("Gaussian tree")
+    return rep
+
+
+def _check_pieces(dump, particles, alpha_min, ids, desc, lo, hi, split_ids, F, rep, n_part, n_rays, rng):
+    import oracle as O
+    L = O.lib()
+    pos = np.asarray(particles["pos"], np.float32)
+    scale = np.asarray(particles["scale"], np.float32)
+    quat = np.asarray(particles["quat"], np.float32)
+    opac = np.asarray(particles["opacity"], np.float32)
+    pick = split_ids if len(split_ids) <= n_part else np.sort(rng.choice(split_ids, n_part, replace=False))
+    o_ = np.argsort(ids, kind="stable")
+    ids_sorted = ids[o_]
+    part = np.zeros(1, O.PARTICLE_DTYPE)
+    fp = C.POINTER(C.c_float)
+    te, tx = C.c_float(), C.c_float()
+    _, tt = tt_constants()
+    worst = np.inf
+    n_events = 0
+    R64 = rot64(quat[pick])
+    A_all = inv_cov32(quat[pick], scale[pick])
+    lo64, hi64 = lo.astype(np.float64), hi.astype(np.float64)
+    for q, i in enumerate(pick):
+        a, b = np.searchsorted(ids_sorted, [i, i + 1])
+        js = o_[a:b]
+        s = np.float32(dump["rec"][js[0], 3])
+        part["pos"], part["scale"], part["quat"], part["opacity"] = pos[i], scale[i], quat[i], opac[i]
+        e = scale[i].astype(np.float64) * float(s) * tt
+        k, p = desc_cells(desc[js])
+        g = p[0]
+        # targets in principal coordinates: random points, points on the planes between cells, points near the silhouette
+        tgt = rng.uniform(-1, 1, (n_rays, 3)) * e
+        ax = rng.integers(0, 3, n_rays)
+        cut = rng.integers(1, np.maximum(g[ax], 2))
+        even = np.arange(n_rays) % 2 == 0                    # every other target on a plane between two cells
+        tgt[even, ax[even]] = -e[ax[even]] + cut[even] * 2 * e[ax[even]] / g[ax[even]]
+        sil = rng.normal(size=(n_rays, 3))
+        sil *= e / np.linalg.norm(sil / e, axis=1, keepdims=True) * 0.93   # on an ellipsoid just inside the proxy: grazing rays
+        tgt = np.concatenate([tgt, sil])
+        dirs = rng.normal(size=(2 * n_rays, 3))
+        dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+        tw = pos[i].astype(np.float64) + tgt @ R64[q].T
+        o32 = (tw - dirs * (4.0 * float(np.linalg.norm(e)))).astype(np.float32)
+        d32 = dirs.astype(np.float32)
+        ts, rays = [], []
+        for r in range(len(o32)):
+            if L.grto_proxy_hit(part.ctypes.data, float(alpha_min), o32[r].ctypes.data_as(fp), d32[r].ctypes.data_as(fp),
+                                C.byref(te), C.byref(tx)):
+                ts += [te.value, tx.value]
+                rays += [r, r]
+        if not ts:
+            continue
+        rays = np.asarray(rays)
+        ts = np.asarray(ts, np.float32)
+        A = A_all[q].reshape(3, 3)
+
+        def mv(v):  # the kernels' matvec: (A0 x + A1 y) + A2 z per row, float32
+            return np.stack([(A[r, 0] * v[:, 0] + A[r, 1] * v[:, 1]) + A[r, 2] * v[:, 2] for r in range(3)], 1).astype(np.float32)
+
+        o_g = mv((o32[rays] - pos[i]).astype(np.float32))
+        d_g = mv(d32[rays])
+        ne = len(ts)
+        n_events += ne
+        P = len(js)
+        cell, cand = piece_owner_cells(np.tile(desc[js], ne), np.full(ne * P, s, np.float32), np.repeat(o_g, P, 0),
+                                       np.repeat(d_g, P, 0), np.repeat(ts, P))
+        kk = np.tile(k, (ne, 1))
+        own = (cell == kk).all(1).reshape(ne, P)
+        n_own = own.sum(1)
+        for ev in np.flatnonzero(n_own != 1)[:3]:
+            F.add("G5", f"particle {i}: the event at t = {ts[ev]!r} of the ray o = {o32[rays[ev]].tolist()} d = {d32[rays[ev]].tolist()} "
+                        f"is owned by {int(n_own[ev])} pieces")
+        cnd = ((kk >= cand[:, :, 0]) & (kk <= cand[:, :, 1])).all(1).reshape(ne, P)
+        pt = o32[rays].astype(np.float64) + ts.astype(np.float64)[:, None] * d32[rays].astype(np.float64)
+        ev, pc = np.nonzero(cnd)
+        j = js[pc]
+        mg = np.minimum(pt[ev] - lo64[j], hi64[j] - pt[ev]) / np.maximum(hi64[j] - lo64[j], 1e-30)
+        mg = mg.min(1)
+        if len(mg):
+            worst = min(worst, float(mg.min()))
+        for x in np.flatnonzero(mg < 0)[:3]:
+            F.add("G5", f"particle {i}: the event at t = {ts[ev[x]]!r} (point {pt[ev[x]].tolist()}) belongs to piece {j[x]} (cell "
+                        f"{k[pc[x]].tolist()}), whose box {lo[j[x]].tolist()} .. {hi[j[x]].tolist()} does not hold it")
+    rep["g5_particles"] = int(len(pick))
+    rep["g5_events"] = int(n_events)
+    rep["g5_min_rel_margin"] = worst if n_events else None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mesh tree
+# ---------------------------------------------------------------------------------------------------------------------
+def tri_boxes32(verts, faces):
+    """the triangle boxes the builder forms (fminf / fmaxf of the corners, then 1e-5 (1 + |coordinate|) outwards), float32"""
+    v = np.asarray(verts, np.float32)[np.asarray(faces, np.int64)]      # [nf][3][3]
+    lo = np.minimum(v[:, 0], np.minimum(v[:, 1], v[:, 2]))
+    hi = np.maximum(v[:, 0], np.maximum(v[:, 1], v[:, 2]))
+    e = np.float32(1e-5) * (np.float32(1) + np.maximum(np.abs(lo), np.abs(hi)))
+    return (lo - e).astype(np.float32), (hi + e).astype(np.float32)
+
+
+def check_mesh_tree(dump, verts, faces):
+    """dump: Tracer.debug_tree(1); verts [nv][3], faces [nf][3] as set (several meshes: concatenated, faces offset)."""
+    F = _Faults()
+    rep = Report()
+    m = dump["n_prims"]
+    verts = np.asarray(verts, np.float32)
+    faces = np.asarray(faces, np.int64)
+    tri = np.asarray(dump["rec"], np.float32)
+    order = np.asarray(dump["order"], np.int64)
+    F.check("G1", [m == len(faces)], lambda i: f"n_prims {m} != {len(faces)} faces")
+    F.check("G1", [len(np.unique(order)) == len(order)], lambda i: "order repeats a face")
+    fid = u32(tri[:, 3]).astype(np.int64)
+    F.check("G6", fid == order, lambda i: f"triangle {i}: face id {fid[i]} != order {order[i]}")
+    want = verts[faces[np.minimum(order, len(faces) - 1)]]                  # [m][3][3]
+    got = tri.reshape(-1, 3, 4)[:, :, :3]
+    F.check("G6", (u32(got) == u32(want)).all((1, 2)), lambda i: f"triangle {i} (face {order[i]}): vertices {got[i].tolist()} != the "
+                                                                 f"uploaded {want[i].tolist()}")
+    lo, hi = tri_boxes32(verts, faces)
+    lo, hi = lo[np.minimum(order, len(faces) - 1)], hi[np.minimum(order, len(faces) - 1)]
+    w64 = want.astype(np.float64)
+    F.check("G4", (lo.astype(np.float64) < w64.min(1)).all(1) & (hi.astype(np.float64) > w64.max(1)).all(1),
+            lambda i: f"triangle {i}: box does not strictly contain its vertices")
+    worder, _, winfo = _walk_binary(dump, F, lo, hi)
+    rep.update(winfo)
+    rep["height"] = dump["height"]
+    F.raise_if_any("mesh tree")
+    return rep
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dumps <-> npz
+# ---------------------------------------------------------------------------------------------------------------------
+SCALARS = ("n_prims", "n_nodes", "height", "root_ref", "leaf_max", "has_pieces", "wide")
+ARRAYS = ("nodes", "wnodes", "qnodes", "pbox", "order", "rec")
+
+
+def dump_to_npz_dict(dump, prefix):
+    out = {f"{prefix}_{k}": np.asarray(dump[k]) for k in ARRAYS}
+    out.update({f"{prefix}_{k}": np.uint32(dump[k]) for k in SCALARS})
+    return out
+
+
+def dump_from_npz(z, prefix):
+    d = {k: int(z[f"{prefix}_{k}"]) for k in SCALARS}
+    d.update({k: np.array(z[f"{prefix}_{k}"]) for k in ARRAYS})
+    return d
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the fixture tests/golden/tree_small.npz (tests/test_bvh_check.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def fixture_scene():
+    """About 1500 synthetic particles, 300 more on coincident centres (equal Morton keys) and twelve scene-sized needles and
+    sheets that the builder cuts into pieces; a reference sphere mesh beside them.  Returns (acts, (verts, normals, faces))."""
+    import grt
+    raw = grt.synth_scene(11, 1500)
+    acts = grt.activate(raw)
+    rng = np.random.default_rng(11)
+    k = 300
+    extra = {"pos": np.repeat(acts["pos"][:1], k, 0), "scale": acts["scale"][rng.integers(0, 1500, k)],
+             "quat": acts["quat"][rng.integers(0, 1500, k)], "opacity": acts["opacity"][rng.integers(0, 1500, k)],
+             "sh": acts["sh"][rng.integers(0, 1500, k)]}
+    q = rng.normal(size=(12, 4)).astype(np.float32)
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    sc = np.full((12, 3), 0.004, np.float32)
+    sc[np.arange(12), np.arange(12) % 3] = np.linspace(0.3, 0.9, 12, dtype=np.float32)
+    sc[9:, 1] = np.float32(0.25)                          # three sheets
+    needles = {"pos": acts["pos"][rng.integers(0, 1500, 12)], "scale": sc, "quat": q,
+               "opacity": np.linspace(0.6, 0.95, 12, dtype=np.float32), "sh": acts["sh"][:12]}
+    acts = {n: np.ascontiguousarray(np.concatenate([acts[n], extra[n], needles[n]]), np.float32) for n in acts}
+    center = grt.gaussian_center(acts["pos"])
+    mesh = grt.sphere_mesh(center + np.float32([0.2, 0.0, 0.4]), 0.25, 40, 20)
+    return acts, mesh
+
+
+def write_fixture(path):
+    """Build the fixture's scene on the GPU and write its particles, Gaussian tree and mesh tree (compressed npz)."""
+    import grt
+    acts, (v, nrm, f) = fixture_scene()
+    tr = grt.Tracer(0)
+    tr.upload(acts)
+    tr.set_meshes([(v, nrm, f)])
+    out = {f"p_{n}": acts[n] for n in ("pos", "scale", "quat", "opacity")}
+    out.update({"mesh_verts": v, "mesh_faces": np.asarray(f, np.uint32), "alpha_min": np.float32(0.01),
+                "n_primitives": np.uint64(tr.bvh_info()["n_primitives"])})
+    out.update(dump_to_npz_dict(tr.debug_tree(0), "g"))
+    out.update(dump_to_npz_dict(tr.debug_tree(1), "m"))
+    tr.close()
+    np.savez_compressed(path, **out)
+
+
+if __name__ == "__main__":
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.join(root, "gaussian-ray-tracing_amd", "python"), os.path.join(root, "oracle")]
+    if len(sys.argv) == 3 and sys.argv[1] == "--write-fixture":
+        write_fixture(sys.argv[2])
+    else:
+        sys.exit("usage: python tests/bvh_check.py --write-fixture tests/golden/tree_small.npz")
