@@ -1521,7 +1521,7 @@ static int size_overflow_pool(grt_ctx* c, uint32_t n_tiles, hipStream_t s)
     return GRT_OK;
 }
 
-static int do_launch(grt_ctx* c, RenderArgs& a, void* stream)
+static int do_launch(grt_ctx* c, RenderArgs& a, void* stream, const AuxOut* px = nullptr)
 {
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     grt_ctx* sc = scene_of(c);
@@ -1683,6 +1683,7 @@ static int do_launch(grt_ctx* c, RenderArgs& a, void* stream)
     aux.aux = c->aux_stream; aux.fork = c->ev_fork; aux.join = c->ev_join;
     aux.heavy_cap = a.n_heavy ? std::max(1u, a.n_units / (uint32_t)c->opt_heavy_cap_div) : 0u; // in scheduling units
     aux.force_big = c->opt_kernel == 4;
+    aux.px = px; // aux frame: launch_render takes the aux kernels (tile aux kernel or per-lane)
     if (tile_kernel) { a.n_heavy = nullptr; aux.heavy_cap = 0; } // no big-window split on the tile kernel
     a.tile_ready_min = (uint32_t)c->opt_tile_ready;
     a.tile_band = (float)c->opt_tile_band / 1024.0f;
@@ -1727,6 +1728,13 @@ static int do_launch(grt_ctx* c, RenderArgs& a, void* stream)
                 fprintf(stderr, "grt order: four-way %u two-way %u first:%s\n", n4, n2, head.c_str());
             }
         }
+    }
+    if (px && !(tile_kernel && a.mode == 0 && !sc->n_faces)) {
+        // an aux frame on the per-lane kernel (launch_render_aux): screen order, no cost words — and the feedback of this slot starts
+        // afresh with the next frame instead of making an order from costs nobody wrote
+        a.order = nullptr; a.n_launch = 0; a.cost = nullptr; a.n_heavy = nullptr;
+        c->cost_valid = false;
+        c->order_ready = false;
     }
     int rc = launch_render(a, c->opt_counters != 0, c->opt_kernel, depth, tile_kernel, s, &aux, &c->err);
     CHK(c, hipEventRecord(c->ev1, s));
@@ -1818,6 +1826,38 @@ int grt_render(grt_ctx* c, const grt_params* p, uint8_t* d_rgb8, float* d_rgbf, 
     return do_launch(c, a, stream);
 }
 
+// aux frames: NULL aux (or three NULL pointers) is the plain call itself; counters have no aux kernels
+static bool aux_wanted(const grt_aux_out* x) { return x && (x->alpha || x->depth || x->count); }
+static int aux_refused(grt_ctx* c, const char* fn)
+{
+    if (!c) return GRT_ERR_INVALID;
+    if (c->opt_counters) {
+        c->err = std::string(fn) + ": aux outputs with GRT_OPT_COUNTERS = 1 (the instrumented kernels have no aux variant)";
+        return GRT_ERR_INVALID;
+    }
+    return GRT_OK;
+}
+
+int grt_render_aux(grt_ctx* c, const grt_params* p, uint8_t* d_rgb8, float* d_rgbf, const grt_aux_out* aux, uint32_t x0, uint32_t y0,
+                   uint32_t x1, uint32_t y1, void* stream)
+{
+    if (!aux_wanted(aux)) return grt_render(c, p, d_rgb8, d_rgbf, x0, y0, x1, y1, stream);
+    int rc = aux_refused(c, "grt_render_aux");
+    if (rc != GRT_OK) return rc;
+    RenderArgs a;
+    rc = fill_common(c, p, &a);
+    if (rc != GRT_OK) return rc;
+    if (x1 > p->width || y1 > p->height || x0 > x1 || y0 > y1) { c->err = "grt_render_aux: window outside the frame"; return GRT_ERR_INVALID; }
+    a.out8 = d_rgb8; a.outf = d_rgbf; // (either may be NULL: the aux outputs alone are a frame)
+    a.mode = 0;
+    a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
+    a.nbx = (x1 - x0 + 15) / 16;
+    a.nby = (y1 - y0 + 15) / 16;
+    a.n_blocks = a.nbx * a.nby;
+    const AuxOut px{aux->alpha, aux->depth, aux->count};
+    return do_launch(c, a, stream, &px);
+}
+
 int grt_render_tiles(grt_ctx* c, const grt_params* p, uint8_t* d_rgb8, float* d_rgbf, uint32_t tile_w, uint32_t tile_h,
                      uint32_t first_tile, uint32_t tile_stride, uint32_t n_tiles, void* stream)
 {
@@ -1881,6 +1921,25 @@ int grt_render_rays(grt_ctx* c, const grt_params* p, const float* d_rays, uint64
     a.rays = d_rays; a.n_rays = n;
     a.n_blocks = (uint32_t)((n + 255) / 256);
     return do_launch(c, a, stream);
+}
+
+int grt_render_rays_aux(grt_ctx* c, const grt_params* p, const float* d_rays, uint64_t n, float* d_rgbf, const grt_aux_out* aux,
+                        void* stream)
+{
+    if (!aux_wanted(aux)) return grt_render_rays(c, p, d_rays, n, d_rgbf, stream);
+    int rc = aux_refused(c, "grt_render_rays_aux");
+    if (rc != GRT_OK) return rc;
+    RenderArgs a;
+    rc = fill_common(c, p, &a);
+    if (rc != GRT_OK) return rc;
+    if (n && !d_rays) { c->err = "grt_render_rays_aux: null ray buffer"; return GRT_ERR_INVALID; }
+    if (n > 0xFFFFFFFFull * 64) { c->err = "grt_render_rays_aux: too many rays"; return GRT_ERR_LIMIT; }
+    a.outf = d_rgbf; // (may be NULL)
+    a.mode = 2;
+    a.rays = d_rays; a.n_rays = n;
+    a.n_blocks = (uint32_t)((n + 255) / 256);
+    const AuxOut px{aux->alpha, aux->depth, aux->count};
+    return do_launch(c, a, stream, &px);
 }
 
 // The sticky device error word (RenderArgs::err_word): a wave that had to give up on a ray — watchdog, depth-first stack

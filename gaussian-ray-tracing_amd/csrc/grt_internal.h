@@ -174,7 +174,16 @@ struct LaunchAux {
     hipEvent_t fork = nullptr, join = nullptr;
     uint32_t heavy_cap = 0; // grid of the big-window launch (0 = no split)
     bool force_big = false; // GRT_OPT_KERNEL = 4: every block on the big-window kernel (testing)
+    const struct AuxOut* px = nullptr; // aux frame (grt_render_aux / grt_render_rays_aux): per-pixel alpha / depth / count
 };
+// Per-pixel outputs beside colour (grt.h: grt_aux_out).  A second kernel argument of the aux kernels only
+// (k_render_tile_aux, k_render_aux): RenderArgs does not grow, so no existing kernel's code moves.  Each pointer may be null.
+struct AuxOut {
+    float* alpha;
+    float* depth;
+    uint32_t* count;
+};
+int launch_render_tile_aux(const RenderArgs& a, const AuxOut& x, hipStream_t stream, std::string* err); // (its own TU)
 int launch_render(const RenderArgs& a, bool count, int kernel_variant, uint32_t stack_depth, bool tile_kernel,
                   hipStream_t stream, const LaunchAux* aux, std::string* err);
 int launch_render_wave(const RenderArgs& a, bool count, hipStream_t stream, std::string* err);

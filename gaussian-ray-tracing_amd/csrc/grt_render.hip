@@ -138,11 +138,20 @@ __device__ __forceinline__ bool gps_round(const RenderArgs& a, uint32_t* __restr
     return true;
 }
 
+// per-ray accumulators of an aux frame (k_render_aux): the ray's first Gaussian segment, grt.h: grt_aux_out
+struct AuxAcc {
+    float depth = 0.0f;  // sum of (T_i alpha_i) t_i
+    uint32_t count = 0u; // its terms
+    float alpha = 0.0f;  // accumAlpha at the end of the bounce loop
+};
+
 // trace() — shaders/tracer.cuh:328-373
-template <bool COUNT, int KK>
+// AUX: acc (null after the first segment) receives the depth terms — the tile aux kernel's expression (grt_render_tile_aux.hip),
+// before T is updated; AUX = false compiles to the code it was before
+template <bool COUNT, int KK, bool AUX = false>
 __device__ __forceinline__ bool trace_gaussians(const RenderArgs& a, uint32_t* __restrict__ stk, f3 o, f3 d,
                                                 float t_min, float t_max, float& density, f3& radiance, Cnt& c,
-                                                uint32_t limit = 0xFFFFFFFFu)
+                                                uint32_t limit = 0xFFFFFFFFu, AuxAcc* acc = nullptr)
 {
     float T = 1.0f - density;
     const float epsT = 1e-9f;
@@ -167,6 +176,12 @@ __device__ __forceinline__ bool trace_gaussians(const RenderArgs& a, uint32_t* _
                 lastT = fmaxf(key_t(kb.key[i]), lastT);
                 const float hitAlpha = kb.alpha[i];
                 if (a.p.alpha_min < hitAlpha) {
+                    if constexpr (AUX) {
+                        if (acc) {
+                            acc->depth += (T * hitAlpha) * key_t(kb.key[i]);
+                            acc->count++;
+                        }
+                    }
                     const uint32_t id = key_id(kb.key[i]);
                     f3 L;
                     if (a.p.sh_degree_max == 0) {
@@ -199,10 +214,13 @@ __device__ __forceinline__ MeshHit mesh_closest(const RenderArgs& a, uint32_t* _
 // seg_budget: iterations ONE Gaussian segment may take; a ray over it stops, *retry receives its state at the start of
 // that iteration (nothing of the iteration is kept, counters included) and *gave_up is set: such a ray is one of the few
 // with hundreds of events, and is finished wave-cooperatively (tile kernel, one ray per wave)
-template <bool COUNT, int KK>
+// AUX (k_render_aux, fresh rays only): acc receives the depth terms of the first segment and accumAlpha at the end
+template <bool COUNT, int KK, bool AUX = false>
 __device__ __forceinline__ f3 shade_ray(const RenderArgs& a, uint32_t* __restrict__ stk, RayState st, Cnt& c,
-                                        uint32_t seg_budget = 0xFFFFFFFFu, RayState* retry = nullptr, bool* gave_up = nullptr)
+                                        uint32_t seg_budget = 0xFFFFFFFFu, RayState* retry = nullptr, bool* gave_up = nullptr,
+                                        AuxAcc* acc = nullptr)
 {
+    AuxAcc* seg_acc = acc; // the first segment's accumulators; null from the second segment on
     f3 curO = st.curO, curD = st.curD;
     f3 accumColor = st.accumColor, directLight = mk3(0, 0, 0);
     float accumAlpha = st.accumAlpha, blocking = st.blocking, density = st.density;
@@ -220,7 +238,9 @@ __device__ __forceinline__ f3 shade_ray(const RenderArgs& a, uint32_t* __restric
         // the single Gaussian segment of this iteration (one call site keeps the kernel small)
         f3 rad;
         const uint32_t limit = (seg_budget == 0xFFFFFFFFu) ? seg_budget : c.iters + seg_budget;
-        if (!trace_gaussians<COUNT, KK>(a, stk, ray_o, ray_d, a.p.t_min, seg_tmax, density, rad, c, limit)) {
+        const bool traced = trace_gaussians<COUNT, KK, AUX>(a, stk, ray_o, ray_d, a.p.t_min, seg_tmax, density, rad, c, limit, seg_acc);
+        if constexpr (AUX) seg_acc = nullptr;
+        if (!traced) {
             c = c0;
             retry->curO = ray_o; retry->curD = ray_d; retry->accumColor = accumColor;
             retry->accumAlpha = accumAlpha; retry->blocking = blocking; retry->density = density0;
@@ -249,6 +269,7 @@ __device__ __forceinline__ f3 shade_ray(const RenderArgs& a, uint32_t* __restric
         timeout += 1;
         if (timeout > kTimeoutIterations) break;
     }
+    if constexpr (AUX) acc->alpha = accumAlpha;
     return accumColor;
 }
 
@@ -589,10 +610,71 @@ __global__ __launch_bounds__(kBlock) void k_render(const RenderArgs a)
     }
 }
 
+// The per-lane kernel of aux frames (grt_render_aux / grt_render_rays_aux): k_render's window (mode 0) and ray-buffer (mode 2)
+// work, with alpha / depth / count beside colour.  Every aux frame the tile aux kernel does not take runs here: mesh frames (the
+// whole bounce loop per lane), ray buffers, GRT_OPT_KERNEL 1-4, trees the tile kernel refuses.  Screen order, no feedback.
+template <int KK>
+__global__ __launch_bounds__(kBlock) void k_render_aux(const RenderArgs a, const AuxOut x)
+{
+    extern __shared__ uint32_t lds_stack[];
+    uint32_t* stk = lds_stack + threadIdx.x;
+    Cnt c;
+    const uint32_t blk = xcd_swizzle(blockIdx.x, a.n_blocks, a.swizzle_chunk);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t lx = (wave & 1u) * 8u + (lane & 7u), ly = (wave >> 1) * 8u + (lane >> 3);
+    size_t out_idx = 0;
+    bool write = false;
+    f3 col = mk3(0.0f, 0.0f, 0.0f);
+    AuxAcc acc;
+    if (a.mode == 2) { // ray buffer
+        const uint64_t i = (uint64_t)blk * kBlock + threadIdx.x;
+        if (i < a.n_rays) {
+            const float* r = a.rays + i * 6;
+            col = shade_ray<false, KK, true>(a, stk, fresh_ray(mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5])), c, 0xFFFFFFFFu, nullptr,
+                                            nullptr, &acc);
+            out_idx = (size_t)i;
+            write = true;
+        }
+    } else { // window of the full frame
+        const uint32_t px = a.x0 + (blk % a.nbx) * 16u + lx;
+        const uint32_t py = a.y0 + (blk / a.nbx) * 16u + ly;
+        write = (px < a.x1) && (py < a.y1);
+        out_idx = (size_t)py * a.p.width + px;
+        if (write) {
+            const f3 nU = mk3(-a.p.U[0], -a.p.U[1], -a.p.U[2]), nV = mk3(-a.p.V[0], -a.p.V[1], -a.p.V[2]);
+            const f3 W = mk3(a.p.W[0], a.p.W[1], a.p.W[2]);
+            f3 dir;
+            bool have_ray = true;
+            if (!a.p.mode_fisheye) get_ray(px, py, nU, nV, W, a.p.width, a.p.height, dir);
+            else have_ray = get_fisheye_ray(px, py, nU, nV, W, a.p.width, a.p.height, dir);
+            if (have_ray)
+                col = shade_ray<false, KK, true>(a, stk, fresh_ray(mk3(a.p.eye[0], a.p.eye[1], a.p.eye[2]), dir), c, 0xFFFFFFFFu, nullptr,
+                                                nullptr, &acc);
+        }
+    }
+    if (write) {
+        if (a.outf) {
+            a.outf[out_idx * 3] = col.x; a.outf[out_idx * 3 + 1] = col.y; a.outf[out_idx * 3 + 2] = col.z;
+        }
+        if (a.out8) {
+            a.out8[out_idx * 3] = quantize8(col.x);
+            a.out8[out_idx * 3 + 1] = quantize8(col.y);
+            a.out8[out_idx * 3 + 2] = quantize8(col.z);
+        }
+        if (x.alpha) x.alpha[out_idx] = acc.alpha;
+        if (x.depth) x.depth[out_idx] = acc.depth;
+        if (x.count) x.count[out_idx] = acc.count;
+    }
+}
+
+static int launch_render_aux(const RenderArgs& a, const AuxOut& x, uint32_t stack_depth, bool tile_kernel, hipStream_t stream,
+                             std::string* err);
+
 int launch_render(const RenderArgs& a, bool count, int kernel_variant, uint32_t stack_depth, bool tile_kernel,
                   hipStream_t stream, const LaunchAux* aux, std::string* err)
 {
     if (a.n_blocks == 0) return GRT_OK;
+    if (aux && aux->px) return launch_render_aux(a, *aux->px, stack_depth, tile_kernel, stream, err);
     const size_t lds = (size_t)kBlock * sizeof(uint32_t) * (stack_depth ? stack_depth : 1);
     const bool wave_ok = (a.mroot == kNoRoot) && (a.mode != 2) && (stack_depth <= 120);
     const bool streaming = uses_stream_kernel(kernel_variant, a.mode, stack_depth); // same test as do_launch's
@@ -726,6 +808,35 @@ int launch_render(const RenderArgs& a, bool count, int kernel_variant, uint32_t 
     e = hipGetLastError();
     if (e != hipSuccess) {
         if (err) *err = std::string("k_render launch: ") + hipGetErrorString(e);
+        return GRT_ERR_HIP;
+    }
+    return GRT_OK;
+}
+
+// (defined behind launch_render: the aux kernel is instantiated last, so every other kernel of this unit keeps its label numbers)
+static int launch_render_aux(const RenderArgs& a, const AuxOut& x, uint32_t stack_depth, bool tile_kernel, hipStream_t stream,
+                             std::string* err)
+{
+    if (a.counters || (a.mode != 0 && a.mode != 2)) {
+        if (err) *err = "aux frame: windows and ray buffers without counters only";
+        return GRT_ERR_INVALID;
+    }
+    // camera rays without meshes where the plain frame runs the tile kernel: its aux instantiation (grt_render_tile_aux.hip)
+    if (tile_kernel && a.mode == 0 && a.mroot == kNoRoot) return launch_render_tile_aux(a, x, stream, err);
+    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * (stack_depth ? stack_depth : 1);
+    if (lds > 160 * 1024) {
+        if (err) *err = "BVH height " + std::to_string(stack_depth) + " needs more than 160 KiB of LDS stack";
+        return GRT_ERR_LIMIT;
+    }
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_render_aux<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        if (err) *err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e);
+        return GRT_ERR_HIP;
+    }
+    hipLaunchKernelGGL(k_render_aux<K>, dim3(a.n_blocks), dim3(kBlock), lds, stream, a, x);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (err) *err = std::string("k_render_aux launch: ") + hipGetErrorString(e);
         return GRT_ERR_HIP;
     }
     return GRT_OK;

@@ -134,6 +134,14 @@ static_assert(kCostFetch % 4u == 0u && kCostTest % 4u == 0u, "the two lowest bit
 #else
 #define GRT_D(f, n)
 #endif
+// Hooks of the aux translation unit (grt_render_tile_aux.hip defines them): accumulators of a ray's first segment, one
+// compositing step (t = the event's key distance, T before the event, alpha), the pixel write.  Empty here: every other
+// instantiation compiles to what it did without them.
+#ifndef GRT_AUX_DECL
+#define GRT_AUX_DECL
+#define GRT_AUX_EVENT(t, T_, ea_)
+#define GRT_AUX_WRITE(idx, have_, dens_)
+#endif
 // The frustum fit uses the hardware reciprocal / reciprocal square root (v_rcp_f32 / v_rsq_f32, 1 ulp) instead of correctly rounded
 // divisions and square roots (a tile re-fits its frustum every time half of its wanting lanes have finished): the per-lane
 // 1 / (d . axis) — (tu, tv) move by 1.2e-7 relative, the bounds are widened by 1e-4; the plane normals — unit to 1.2e-7, against the
@@ -340,9 +348,20 @@ __device__ __forceinline__ void mesh_primary_fused(const RenderArgs& a, uint32_t
     r2 = make_float4(nrm_.x, nrm_.y, nrm_.z, 0.0f);
 }
 
+#ifndef GRT_TILE_AUX_TU
 template <bool COUNT, bool SH, bool MESH, int MODE, bool PIECES>
 __global__ __launch_bounds__(kWG, MODE == 2 ? GRT_TILE_WAVES2 : (MODE == 3 ? kWavesQuad : kWavesPerSimd)) void k_render_tile(const RenderArgs a)
+#else
+// grt_render_tile_aux.hip: the camera-ray kernel of aux frames (MODE 0, no meshes, no counters) — the same body, plus the
+// hooks GRT_AUX_DECL / GRT_AUX_EVENT / GRT_AUX_WRITE that accumulate and write per-pixel alpha, depth and count
+template <bool SH, bool PIECES>
+__global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const RenderArgs a, const AuxOut ax)
+#endif
 {
+#ifdef GRT_TILE_AUX_TU
+    constexpr bool COUNT = false, MESH = false;
+    constexpr int MODE = 0;
+#endif
     constexpr bool BUNDLE = MODE == 1 || MODE == 2, SINGLE = MODE == 2;
     // MODE 3 (QUAD): camera rays of ONE 4x4 QUADRANT of a heavy tile, lanes = rays x slots: lane 4 r + s carries ray r (16 of them) and
     // is its slot s.  The exact work turns round as in MODE 2, but four-fold instead of sixty-four-fold: a trip of the exact-test loop
@@ -517,6 +536,7 @@ __global__ __launch_bounds__(kWG, MODE == 2 ? GRT_TILE_WAVES2 : (MODE == 3 ? kWa
     }
     bool gave_up = false; // MODE 1: the chunk went over its budget
     float density = 0.0f;
+    GRT_AUX_DECL
     // MODE 2 keeps its ray until it ends: every trip of this loop is one iteration of the reference's bounce loop
     // (shaders/tracer.cu:58-106); the other modes make one trip and queue the rays that go on
     for (;;) {
@@ -1006,6 +1026,7 @@ __global__ __launch_bounds__(kWG, MODE == 2 ? GRT_TILE_WAVES2 : (MODE == 3 ? kWa
                             if (COUNT && (!QUAD || own_)) c.hit_evals++;
                             last_key = ek | kCellMask; // nothing with the same (t, id, exit) can compare above it
                             if (a.p.alpha_min < ea) {
+                                GRT_AUX_EVENT(key_t(ek), T, ea)
                                 if (!SH) { // degree 0: the colour load is still in flight; its use waits until the re-key is done
                                     blend_ = true;
                                     T_old = T;
@@ -1562,6 +1583,7 @@ __global__ __launch_bounds__(kWG, MODE == 2 ? GRT_TILE_WAVES2 : (MODE == 3 ? kWa
             a.out8[out_idx * 3 + 1] = quantize8(col.y);
             a.out8[out_idx * 3 + 2] = quantize8(col.z);
         }
+        GRT_AUX_WRITE(out_idx, have_ray, density)
     }
 #ifdef GRT_TILE_DIAG
     if (COUNT) { c = (lane == 0) ? w : Cnt(); c.fetches = w.fetches; }
@@ -1647,6 +1669,36 @@ int launch_render_tile_single(const RenderArgs& a, bool count, hipStream_t strea
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         if (err) *err = std::string("k_render_tile (one ray per wave) launch: ") + hipGetErrorString(e);
+        return GRT_ERR_HIP;
+    }
+    return GRT_OK;
+}
+#elif defined(GRT_TILE_AUX_TU)
+// ---- this translation unit (grt_render_tile_aux.hip) holds the camera-ray kernel of aux frames: what launch_render_tile runs for
+//      mode 0 without meshes, plus per-pixel alpha / depth / count.  The four-way parts of heavy tiles run as part waves of this
+//      kernel (no quad kernel beside it: as with GRT_OPT_QUAD_PARTS = 0, the same pixels) ----
+int launch_render_tile_aux(const RenderArgs& a, const AuxOut& x, hipStream_t stream, std::string* err)
+{
+    if (a.n_blocks == 0) return GRT_OK;
+    if (a.root_ref != kNoRoot && (!a.pbox || (!(a.root_ref & kLeafBit) && !a.qnodes) || !a.erec)) {
+        if (err) *err = "tile kernel: per-child BVH layout or eye records missing";
+        return GRT_ERR_INVALID;
+    }
+    if (a.mode != 0 || a.mroot != kNoRoot || a.counters) {
+        if (err) *err = "tile aux kernel: camera-ray windows without meshes or counters only";
+        return GRT_ERR_INVALID;
+    }
+    const bool sh = a.p.sh_degree_max > 0, pieces = a.has_pieces != 0u;
+    RenderArgs b = a;
+    b.heavy_role = 0;
+    b.quad_parts = 0u;
+    void (*k)(const RenderArgs, const AuxOut) = sh ? (pieces ? k_render_tile_aux<true, true> : k_render_tile_aux<true, false>)
+                                                   : (pieces ? k_render_tile_aux<false, true> : k_render_tile_aux<false, false>);
+    const uint32_t grid = (a.order && a.n_launch) ? a.n_launch : a.n_blocks * 4u;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kWG), 0, stream, b, x);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (err) *err = std::string("k_render_tile_aux launch: ") + hipGetErrorString(e);
         return GRT_ERR_HIP;
     }
     return GRT_OK;

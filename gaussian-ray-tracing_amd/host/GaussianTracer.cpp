@@ -84,6 +84,20 @@ void GaussianTracer::render(CUDAOutputBuffer& output_buffer) // src/GaussianTrac
     check(grt_sync(m_ctx), "render");
 }
 
+void GaussianTracer::renderAux(CUDAOutputBuffer& output_buffer, float* d_alpha, float* d_depth, unsigned int* d_count)
+{
+    uchar3* result = output_buffer.map();
+    params.output_buffer = result;
+    grt_params p{};
+    fillParams(&p);
+    const grt_aux_out aux{d_alpha, d_depth, reinterpret_cast<uint32_t*>(d_count)};
+    check(grt_render_aux(m_ctx, &p, reinterpret_cast<uint8_t*>(result), nullptr, &aux, 0, 0, params.width, params.height, stream),
+          "grt_render_aux");
+    output_buffer.unmap();
+    hipglue::streamSync(stream);
+    check(grt_sync(m_ctx), "renderAux");
+}
+
 void GaussianTracer::fillParams(void* out) const // Params (src/Parameters.h:42-74) -> the C ABI's grt_params
 {
     grt_params& p = *static_cast<grt_params*>(out);

@@ -24,6 +24,9 @@ public:
     void initialize() { initializeOptix(); }
 
     void render(CUDAOutputBuffer& output_buffer); // CUDAOutputBuffer = HIPOutputBuffer (HIPOutputBuffer.h)
+    // (new) render() plus per-pixel opacity, expected depth and hit count (grt_render_aux; definitions in include/grt.h):
+    // d_alpha / d_depth float[height][width], d_count uint32[height][width] device buffers, each may be null
+    void renderAux(CUDAOutputBuffer& output_buffer, float* d_alpha, float* d_depth, unsigned int* d_count);
 
     void updateCamera(Camera& camera, bool& camera_changed);
     void updateInstanceTransforms(Primitive& p);

@@ -52,6 +52,11 @@ class MemoryInfo(C.Structure):
                 ("overflow_chunks", C.c_uint32), ("overflow_demand", C.c_uint32)]
 
 
+class AuxOut(C.Structure):
+    """grt_aux_out (include/grt.h): device pointers of the per-pixel alpha / depth / count arrays, each may be NULL."""
+    _fields_ = [("alpha", C.c_void_p), ("depth", C.c_void_p), ("count", C.c_void_p)]
+
+
 class Gaussians(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "sh")]
 
@@ -82,7 +87,8 @@ KERNEL_AUTO, KERNEL_PERLANE, KERNEL_WAVE, KERNEL_STREAM, KERNEL_STREAM_BIG, KERN
 
 EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
-    "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_sync",
+    "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
+    "grt_render_rays_aux", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -126,6 +132,8 @@ def lib():
         L.grt_render_tiles.argtypes = [vp, C.POINTER(Params), vp, vp, u32, u32, u32, u32, u32, vp]
         L.grt_assemble_tiles.argtypes = [vp, vp, u32, u32, u32, u32, u32, u32, vp, vp]
         L.grt_render_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp]
+        L.grt_render_aux.argtypes = [vp, C.POINTER(Params), vp, vp, C.POINTER(AuxOut), u32, u32, u32, u32, vp]
+        L.grt_render_rays_aux.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(AuxOut), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -421,6 +429,48 @@ class Tracer:
             out = t.zeros((rays.shape[0], 3), dtype=t.float32, device=rays.device)
         self._check(lib().grt_render_rays(self._h, C.byref(params), rays.data_ptr(), rays.shape[0], out.data_ptr(),
                                           self._stream()))
+        return out
+
+    def _aux_buffers(self, shape, dev, alpha, depth, count):
+        t = self._torch
+        out = {}
+        if alpha:
+            out["alpha"] = t.zeros(shape, dtype=t.float32, device=dev)
+        if depth:
+            out["depth"] = t.zeros(shape, dtype=t.float32, device=dev)
+        if count:
+            out["count"] = t.zeros(shape, dtype=t.uint32, device=dev)
+        ptrs = AuxOut(*(out[k].data_ptr() if k in out else None for k in ("alpha", "depth", "count")))
+        return out, ptrs
+
+    def render_aux(self, params, window=None, want_u8=True, want_f32=False, alpha=True, depth=True, count=True):
+        """A frame with per-pixel opacity, expected depth and hit count beside colour (grt_render_aux; definitions in include/grt.h).
+        Returns a dict of torch tensors: 'u8' [h][w][3] / 'f32' [h][w][3] (when wanted), 'alpha' / 'depth' float32 [h][w], 'count'
+        uint32 [h][w] (when asked for).  Pixels outside the window stay 0.  depth / alpha is the mean distance of the first segment."""
+        t = self._torch
+        w, h = params.width, params.height
+        dev = f"cuda:{self.device}"
+        out, ptrs = self._aux_buffers((h, w), dev, alpha, depth, count)
+        if want_u8:
+            out["u8"] = t.zeros((h, w, 3), dtype=t.uint8, device=dev)
+        if want_f32:
+            out["f32"] = t.zeros((h, w, 3), dtype=t.float32, device=dev)
+        x0, y0, x1, y1 = window if window else (0, 0, w, h)
+        self._check(lib().grt_render_aux(self._h, C.byref(params), out["u8"].data_ptr() if want_u8 else None,
+                                         out["f32"].data_ptr() if want_f32 else None, C.byref(ptrs), x0, y0, x1, y1,
+                                         self._stream()))
+        return out
+
+    def render_rays_aux(self, params, rays, want_f32=True, alpha=True, depth=True, count=True):
+        """grt_render_rays_aux: rays [n][6] (device, float32 o, d) -> dict of 'f32' [n][3] and 'alpha' / 'depth' / 'count' [n]
+        (depth in units of |d|)."""
+        t = self._torch
+        n = rays.shape[0]
+        out, ptrs = self._aux_buffers((n,), rays.device, alpha, depth, count)
+        if want_f32:
+            out["f32"] = t.zeros((n, 3), dtype=t.float32, device=rays.device)
+        self._check(lib().grt_render_rays_aux(self._h, C.byref(params), rays.data_ptr(), n,
+                                              out["f32"].data_ptr() if want_f32 else None, C.byref(ptrs), self._stream()))
         return out
 
     def counters(self):

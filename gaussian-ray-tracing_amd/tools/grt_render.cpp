@@ -93,12 +93,31 @@ static void write_npy(const std::string& path, const unsigned char* rgb, unsigne
     f.write(reinterpret_cast<const char*>(rgb), (std::streamsize)((size_t)w * h * 3));
 }
 
+// NumPy .npy v1.0 of a [h][w] float32 ('<f4') or uint32 ('<u4') array (--alpha / --depth / --count)
+static void write_npy_2d(const std::string& path, const void* data, const char* descr, unsigned int w, unsigned int h)
+{
+    std::string hdr = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" + std::to_string(h) + ", " + std::to_string(w) + "), }";
+    while ((10 + hdr.size() + 1) % 64) hdr.push_back(' ');
+    hdr.push_back('\n');
+    std::ofstream f(path, std::ios::binary);
+    const unsigned char magic[8] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0};
+    f.write(reinterpret_cast<const char*>(magic), 8);
+    const unsigned char len[2] = {(unsigned char)(hdr.size() & 0xFF), (unsigned char)(hdr.size() >> 8)};
+    f.write(reinterpret_cast<const char*>(len), 2);
+    f.write(hdr.data(), (std::streamsize)hdr.size());
+    f.write(reinterpret_cast<const char*>(data), (std::streamsize)((size_t)w * h * 4));
+}
+
 static void usage()
 {
     std::puts("usage: grt_render [-p|--ply scene.ply] [--width W] [--height H] [--fisheye] [--type mirror|normal|glass]\n"
               "                  [--sh-degree 0..3] [--plane] [--sphere] [--obj mesh.obj] [--bounces N]\n"
               "                  [--eye x y z] [--fov deg] [--out frame.ppm|frame.png|frame.npy] [--raw frame.rgb]\n"
               "                  [--move dx dy dz] [--bench N] [--gpus N] [--devices d0,d1,...] [--gather rccl|peer]\n"
+              "                  [--alpha a.npy] [--depth d.npy] [--count c.npy]\n"
+              "  --alpha / --depth / --count: per-pixel opacity, expected depth (sum of T alpha t over the first Gaussian segment) and\n"
+              "            hit count as [H][W] float32 / float32 / uint32 arrays in the renderer's row order (include/grt.h:\n"
+              "            grt_aux_out); one GPU only\n"
               "  --gpus N: the frame's 32x32 tiles are dealt round-robin to N GPUs of this node (one GaussianTracer and one host\n"
               "            thread per GPU, scene replicated), the tile buffers are copied to the first GPU over xGMI and un-permuted\n"
               "            there.  --devices names the GPUs (default 0..N-1; a device may repeat: ranks then share it).\n"
@@ -109,7 +128,7 @@ static void usage()
 
 int main(int argc, char** argv)
 {
-    std::string ply = "../data/train.ply", out, obj, raw_out;
+    std::string ply = "../data/train.ply", out, obj, raw_out, alpha_out, depth_out, count_out;
     float move[3] = {0.0f, 0.0f, 0.0f};
     bool have_move = false;
     unsigned int width = 1280, height = 720, sh_degree = 0, bounces = 32;
@@ -135,6 +154,9 @@ int main(int argc, char** argv)
         else if (a == "--eye") { need(3); for (int k = 0; k < 3; k++) eye[k] = (float)std::atof(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
         else if (a == "--raw") { need(1); raw_out = argv[++i]; }
+        else if (a == "--alpha") { need(1); alpha_out = argv[++i]; }
+        else if (a == "--depth") { need(1); depth_out = argv[++i]; }
+        else if (a == "--count") { need(1); count_out = argv[++i]; }
         else if (a == "--move") { need(3); for (int k = 0; k < 3; k++) move[k] = (float)std::atof(argv[++i]); have_move = true; }
         else if (a == "--bench") { need(1); bench = std::atoi(argv[++i]); }
         else if (a == "--gpus") { need(1); gpus = std::max(1, std::atoi(argv[++i])); }
@@ -149,6 +171,11 @@ int main(int argc, char** argv)
             type = t == "mirror" ? MIRROR : t == "normal" ? NORMAL : t == "glass" ? GLASS : -1;
             if (type < 0) { usage(); return 2; }
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(); return 2; }
+    }
+    const bool want_aux = !alpha_out.empty() || !depth_out.empty() || !count_out.empty();
+    if (want_aux && (gpus > 1 || devices.size() > 1 || !gather.empty())) {
+        std::fprintf(stderr, "--alpha / --depth / --count: one GPU only (tile-sharded frames have no aux outputs)\n");
+        return 2;
     }
     try {
         if (devices.empty()) for (int k = 0; k < gpus; k++) devices.push_back(k);
@@ -219,7 +246,12 @@ int main(int argc, char** argv)
             hipglue::setDevice(tracer.device());
             gathered = static_cast<unsigned char*>(hipglue::deviceAlloc((size_t)gpus * max_cnt * tile_bytes));
         }
+        const size_t npx = (size_t)width * height;
+        float* d_alpha = !alpha_out.empty() ? static_cast<float*>(hipglue::deviceAlloc(npx * 4)) : nullptr;
+        float* d_depth = !depth_out.empty() ? static_cast<float*>(hipglue::deviceAlloc(npx * 4)) : nullptr;
+        unsigned int* d_count = !count_out.empty() ? static_cast<unsigned int*>(hipglue::deviceAlloc(npx * 4)) : nullptr;
         auto frame = [&] {
+            if (want_aux) { tracer.renderAux(output_buffer, d_alpha, d_depth, d_count); return; }
             if (!tiled) { tracer.render(output_buffer); return; }
             per_rank([&](int k, GaussianTracer& t) {
                 const unsigned int cnt = (unsigned int)(bytes_of_rank[(size_t)k] / tile_bytes);
@@ -255,6 +287,15 @@ int main(int argc, char** argv)
         for (int k = 0; k < gpus; k++) { if (mine[(size_t)k]) { hipglue::setDevice(devices[(size_t)k]); hipglue::deviceFree(mine[(size_t)k]); } }
         hipglue::setDevice(tracer.device());
         hipglue::deviceFree(gathered);
+        const std::pair<const std::string*, const void*> aux_files[3] = {{&alpha_out, d_alpha}, {&depth_out, d_depth}, {&count_out, d_count}};
+        for (int k = 0; k < 3; k++) {
+            if (aux_files[k].first->empty()) continue;
+            std::vector<uint32_t> h(npx);
+            hipglue::copyToHost(h.data(), aux_files[k].second, npx * 4);
+            write_npy_2d(*aux_files[k].first, h.data(), k == 2 ? "<u4" : "<f4", width, height);
+            hipglue::deviceFree(const_cast<void*>(aux_files[k].second));
+            std::cout << "wrote " << *aux_files[k].first << "\n";
+        }
         hipglue::rcclDestroy(rccl);
         if (!raw_out.empty()) { // the buffer as the renderer wrote it (row 0 first), from the pinned mirror render() filled
             std::ofstream f(raw_out, std::ios::binary);

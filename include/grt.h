@@ -303,6 +303,37 @@ GRT_API int grt_assemble_tiles(grt_ctx* ctx, const uint8_t* d_gathered, uint32_t
 /* d_rays[n][6] = origin, direction (device); d_rgbf[n][3] */
 GRT_API int grt_render_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, float* d_rgbf,
                             void* stream);
+/* ---- aux outputs: per-pixel (per-ray) opacity, expected depth and hit count beside colour ----
+ * What 3DGRT-style renderers return as pred_opacity / pred_dist / hits_count.  Each array holds one value per pixel, row-major
+ * y*width+x like d_rgbf (grt_render_rays_aux: one per ray).  Device pointers; each may be NULL.
+ *   alpha  (float32) the reference's accumAlpha at the end of the raygen loop (shaders/tracer.cu:58-106; kept at :81 and :97,
+ *          its input is the density trace() returns, shaders/tracer.cuh:372).  Without meshes: clamp(0 + (1 - T_final), 0, 1).
+ *          Mesh frames: summed over the segments with the reference's own clamps (renderNormal's terminate adds alpha and 1 - alpha
+ *          unclamped, shaders/tracer.cuh:417-428).
+ *   depth  (float32) sum over the events composited in the ray's FIRST Gaussian segment — t_min to the first mesh hit, or to t_max
+ *          when there is none — of (T_i alpha_i) t_i: t_i the event's distance as the k-buffer orders it (the entry or the exit
+ *          face of the proxy: the hit.distance trace() folds into rayLastHitDistance, shaders/tracer.cuh:354; both events of a
+ *          particle count), T_i the transmittance before the event, alpha_i its alpha.  Only events with alpha_min < alpha_i count
+ *          (tracer.cuh:361), repeats of a split particle's pieces are dropped as for colour.  Evaluated as (T * alpha) * t in
+ *          float32, before T is updated, and added in compositing order: the same bits on every kernel.  NOT normalised:
+ *          depth / alpha is the mean distance, in world units for camera rays (unit directions) and in units of |d| for
+ *          caller-supplied rays.  (Not the distance of the peak response: DESIGN.md 5.7.)
+ *   count  (uint32) the number of terms of that sum.
+ *   Fisheye pixels with r > 1 receive 0, 0, 0; pixels outside the window are not written (as for colour).
+ * aux == NULL, or all three pointers NULL: exactly grt_render / grt_render_rays.  Either colour buffer may be NULL on an aux frame.
+ * GRT_OPT_COUNTERS = 1 together with an aux output: GRT_ERR_INVALID.  Camera-ray frames without meshes run the tile kernel's aux
+ * instantiation (four-way parts as part waves, no quad kernel); mesh frames, ray buffers, GRT_OPT_KERNEL 1-4 and trees the tile
+ * kernel refuses run the per-lane aux kernel (mesh frames: the whole bounce loop per lane).  Colour is bit-identical to the plain
+ * call's.  grt_render_tiles / multi-GPU frames have no aux outputs. */
+typedef struct {
+    float* alpha;
+    float* depth;
+    uint32_t* count;
+} grt_aux_out;
+GRT_API int grt_render_aux(grt_ctx* ctx, const grt_params* p, uint8_t* d_rgb8, float* d_rgbf, const grt_aux_out* aux,
+                           uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_render_rays_aux(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, float* d_rgbf,
+                                const grt_aux_out* aux, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
