@@ -39,6 +39,31 @@ def shift_macro(ks):
     return ('#define SLOT_SHIFT_ALL(MASK)  \\\n    {  \\\n        const uint64_t m_ = (MASK);  \\\n        uint64_t sv_;  \\\n'
             + '  \\\n'.join(body.split('\n')) + '  \\\n    }\n')
 
+def shift_macro_chain(ks):
+    """ONE asm statement for the whole window (8 / 12 slots): EXEC is narrowed to MASK once and restored once, and the
+    test that ends the walk between blocks (no lane holds a key at the block's first slot) is a v_cmp + branch inside
+    the statement.  The block form above saves and restores EXEC per block: two scalar instructions per block and
+    compositing step more.  The test runs under the narrowed EXEC — over the lanes that shift, the only ones it matters
+    for (a lane outside MASK moves nothing)."""
+    assert ks % 4 == 0 and ks <= 12
+    L = ['s_and_saveexec_b64 %[sv], %[m]']
+    for lo in range(0, ks, 4):
+        if lo:
+            L.append(f'v_cmp_ne_u64 vcc, -1, %[k{lo}]')
+            L.append('s_cbranch_vccz .Lgrt_sx_%=')
+        for i in range(lo, lo + 4):
+            L.append(f'v_mov_b64 %[k{i}], ' + (f'%[k{i+1}]' if i + 1 < ks else '-1'))
+    L.append('.Lgrt_sx_%=:')
+    L.append('s_mov_b64 exec, %[sv]')
+    return L
+
+def shift_macro_v2(ks):
+    L = shift_macro_chain(ks)
+    body = ' '.join('"' + l + '\\n\\t"' for l in L[:-1]) + ' "' + L[-1] + '"'
+    outs = ', '.join(f'[k{i}] "+v"(k{i})' for i in range(ks)) + ', [sv] "=&s"(sv_)'
+    return ('#define SLOT_SHIFT_ALL(MASK)  \\\n    {  \\\n        const uint64_t m_ = (MASK);  \\\n        uint64_t sv_;  \\\n'
+            '        asm volatile(' + body + '  \\\n                     : ' + outs + '  \\\n                     : [m] "s"(m_)  \\\n                     : "vcc", "scc");  \\\n    }\n')
+
 def insert_macro(ks):
     """Per block: all the compares first (KEY against the ORIGINAL keys k[hi] .. k[lo-1], independent VALU ops whose
     SGPR results are ready by the time the moves need them), then the EXEC-masked moves."""
@@ -156,6 +181,6 @@ def insert_macro_v2(ks):
 print('// GENERATED by gen_slots.py — do not edit; see that file for what these macros do and why.')
 for ks in (8, 12, 32):
     print(f'#if GRT_KS == {ks}')
-    print(shift_macro(ks))
+    print(shift_macro(ks) if ks > 12 else shift_macro_v2(ks))
     print(insert_macro(ks) if ks > 12 else insert_macro_v2(ks))
     print('#endif')

@@ -908,14 +908,18 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                     uint64_t limk_ = (bagmin < lost) ? bagmin : lost;
                     if (QUAD) limk_ = quad_umin64(limk_);
                     limk_ = (fkey_ < limk_) ? fkey_ : limk_;
+                    // For the length of the sweeps `alive` is a lane MASK, am_, and the conditions of a step are formed as masks
+                    // (votes on single compares, scalar algebra) and read per lane through lane_of(): a per-lane bool that is
+                    // also voted on costs the vote and, carried round the loop, three scalar operations per trip to merge.
+                    // A tile without bags (most: `bags` is wave-uniform) skips everything that mentions one.
+                    uint64_t am_ = wave_ballot(alive);
+                    // a lane whose next final event sits in its bag needs a refill before it can go on
+#define GRT_NEED_(CM) (lane_of(am_ & ~(CM)) && (nb != 0u) && (key_t(bagmin) < F) && (bagmin < lost) && ((q0_ == kKeyInvalid) || (q0_ >= bagmin)))
                     while (true) {
                         uint64_t q0_ = QUAD ? quad_umin64(k0) : k0;
-                        bool can_ = alive & (q0_ < limk_);
-                        uint64_t cm_ = wave_ballot(alive) & wave_ballot(q0_ < limk_);
-                        // a lane whose next final event sits in its bag needs a refill before it can go on
-                        const bool need = bags && alive && (nb != 0u) && !can_ && (key_t(bagmin) < F) && (bagmin < lost) &&
-                                          ((q0_ == kKeyInvalid) || (q0_ >= bagmin));
-                        const uint64_t nm_ = bags ? wave_ballot(need) : 0ull;
+                        uint64_t cm_ = am_ & vote_lt_u64(q0_, limk_);
+                        uint64_t nm_ = 0ull;
+                        if (bags) nm_ = wave_ballot(GRT_NEED_(cm_));
                         if (!(cm_ | nm_)) break;
                         // A sweep starts — and goes on — while enough lanes can take part: half of the WANTING lanes, at most
                         // ready_min (a tile down to a few wanting lanes never has ready_min of them ready: its last rays would go
@@ -932,7 +936,7 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                             if (QUAD && nm_) { nmq_ |= (nmq_ & 0xAAAAAAAAAAAAAAAAull) >> 1; nmq_ |= (nmq_ & 0x5555555555555555ull) << 1;
                                                nmq_ |= (nmq_ & 0xCCCCCCCCCCCCCCCCull) >> 2; nmq_ |= (nmq_ & 0x3333333333333333ull) << 2; }
                             const bool go_ = ((uint32_t)__popcll(cm_ | nmq_) >= rmin_) ||
-                                             wave_any(can_ && ((KPRESS != kKeyInvalid) || (T < kSweepEagerT)));
+                                             ((cm_ & (vote_ne_u64(KPRESS, kKeyInvalid) | vote_lt_f32(T, kSweepEagerT))) != 0ull);
                             if (!go_) break;
                         }
                         if (!cm_) {
@@ -942,7 +946,7 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                             GRT_D(node_visits, 1)
                             // lanes that do not need it yet but have room for four more keys come along: one scan instead
                             // of one per lane a few steps apart
-                            const bool rf = need || (alive && (nb != 0u) && (KROOM == kKeyInvalid) && (bagmin < lost));
+                            const bool rf = GRT_NEED_(0ull) || (lane_of(am_) && (nb != 0u) && (KROOM == kKeyInvalid) && (bagmin < lost));
                             uint32_t nmax = rf ? nb : 0u;
                             for (int off = 32; off > 0; off >>= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, off));
                             nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmax);
@@ -990,10 +994,10 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                             if (QUAD) limk_ = quad_umin64(limk_);
                             limk_ = (fkey_ < limk_) ? fkey_ : limk_;
                             q0_ = QUAD ? quad_umin64(k0) : k0;
-                            can_ = alive & (q0_ < limk_);
-                            cm_ = wave_ballot(alive) & wave_ballot(q0_ < limk_);
+                            cm_ = am_ & vote_lt_u64(q0_, limk_);
                         }
                         if (!cm_) continue;
+                        const bool can_ = lane_of(cm_);
                         GRT_D(hit_evals, 1)
                         const uint64_t ek = q0_;
                         const uint32_t cell = (uint32_t)(ek & kCellMask);
@@ -1020,32 +1024,32 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
 #endif
                         // equal keys meet in the window when a split particle was inserted through two of its pieces: the first is
                         // composited, the repeat only gives its cell back
-                        const bool dup_ = PIECES && can_ && ((ek | kCellMask) == last_key);
-                        const uint64_t dupm_ = PIECES ? wave_ballot((ek | kCellMask) == last_key) : 0ull;
-                        if (can_ && !dup_) { // shaders/tracer.cuh:352-367
-                            if (COUNT && (!QUAD || own_)) c.hit_evals++;
-                            last_key = ek | kCellMask; // nothing with the same (t, id, exit) can compare above it
-                            if (a.p.alpha_min < ea) {
-                                GRT_AUX_EVENT(key_t(ek), T, ea)
-                                if (!SH) { // degree 0: the colour load is still in flight; its use waits until the re-key is done
-                                    blend_ = true;
-                                    T_old = T;
-                                } else {
-                                    f3 dl = dn; // keep the SH basis out of loop-invariant hoisting (it would spill)
-                                    asm volatile("" : "+v"(dl.x), "+v"(dl.y), "+v"(dl.z));
-                                    const f3 L = sh_radiance(a.sh + (size_t)id * 48, dl, a.p.sh_degree_max);
-                                    radiance = add3(radiance, mul3s(mul3s(L, T), ea));
-                                }
-                                T *= (1.0f - ea);
-                            }
-                            if (!(T > minT)) alive = false;
+                        const uint64_t dupm_ = PIECES ? vote_eq_u64(ek | kCellMask, last_key) : 0ull;
+                        // the event proper (shaders/tracer.cuh:352-367), in the lanes of evm_; blm_: the ones it changes T in.  Selects,
+                        // not a per-lane block: the block is three vector operations and costs an EXEC save, narrowing and restore
+                        const uint64_t evm_ = cm_ & ~dupm_;
+                        const uint64_t blm_ = evm_ & vote_lt_f32(a.p.alpha_min, ea);
+                        const bool ev_ = lane_of(evm_), bl_ = lane_of(blm_);
+                        if (COUNT && ev_ && (!QUAD || own_)) c.hit_evals++;
+                        last_key = ev_ ? (ek | kCellMask) : last_key; // nothing with the same (t, id, exit) can compare above it
+                        if (bl_) { GRT_AUX_EVENT(key_t(ek), T, ea) }
+                        if (!SH) { // degree 0: the colour load is still in flight; its use waits until the re-key is done
+                            blend_ = bl_;
+                            T_old = T;
+                        } else if (bl_) {
+                            f3 dl = dn; // keep the SH basis out of loop-invariant hoisting (it would spill)
+                            asm volatile("" : "+v"(dl.x), "+v"(dl.y), "+v"(dl.z));
+                            const f3 L = sh_radiance(a.sh + (size_t)id * 48, dl, a.p.sh_degree_max);
+                            radiance = add3(radiance, mul3s(mul3s(L, T), ea));
                         }
+                        T = bl_ ? T * (1.0f - ea) : T;
+                        am_ &= ~(evm_ & vote_nle_f32(T, minT));
                         // an entry whose exit lies inside the segment is re-keyed to its exit event and keeps its
                         // payload cell, otherwise the cell is released
-                        const bool rekey = can_ && own_ && !dup_ && ((((uint32_t)ek) & 32u) == 0u) && (eo < t_hi);
-                        const uint64_t nk = rekey ? (mk_skey(eo, id, 1) | (uint64_t)cell) : kKeyInvalid;
-                        pmask = (can_ && own_ && !rekey) ? (pmask & ~(1u << cell)) : pmask;
                         const uint64_t rkm_ = ownm_ & ~dupm_ & vote_eq_u32(((uint32_t)ek) & 32u, 0u) & vote_lt_f32(eo, t_hi);
+                        const bool rekey = lane_of(rkm_);
+                        const uint64_t nk = rekey ? (mk_skey(eo, id, 1) | (uint64_t)cell) : kKeyInvalid;
+                        pmask = lane_of(ownm_ & ~rkm_) ? (pmask & ~(1u << cell)) : pmask;
                         if (rkm_) { // wave-uniform branch
                             if (rekey) PL_OTHER(cell) = INFINITY;
                             SLOT_INSERT(nk) // a slot was just freed: it fits
@@ -1054,6 +1058,8 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                         //  color0 has the window pop and the re-key to hide behind)
                         if (!SH && blend_) radiance = add3(radiance, mul3s(mul3s(mk3(cc.x, cc.y, cc.z), T_old), ea));
                     }
+#undef GRT_NEED_
+                    alive = lane_of(am_);
                 }
                 if (done) break;
                 // watchdog: never reached by design; a reported failure beats a hung GPU.  HOW it is reported matters: any

@@ -137,6 +137,49 @@ __device__ __forceinline__ uint64_t vote_lt_f32(float a, float b)
     return a < b;
 #endif
 }
+__device__ __forceinline__ uint64_t vote_nle_f32(float a, float b) // !(a > b): true for a NaN
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fcmpf(a, b, 13); // FCMP_ULE
+#else
+    return !(a > b);
+#endif
+}
+__device__ __forceinline__ uint64_t vote_lt_u64(uint64_t a, uint64_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_uicmpl(a, b, 36); // ICMP_ULT
+#else
+    return a < b;
+#endif
+}
+__device__ __forceinline__ uint64_t vote_eq_u64(uint64_t a, uint64_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_uicmpl(a, b, 32); // ICMP_EQ
+#else
+    return a == b;
+#endif
+}
+__device__ __forceinline__ uint64_t vote_ne_u64(uint64_t a, uint64_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_uicmpl(a, b, 33); // ICMP_NE
+#else
+    return a != b;
+#endif
+}
+// a lane mask as a per-lane condition: bit `lane` of m (m wave-uniform).  No instruction: the SGPR pair is used as the
+// condition of the select or the EXEC narrowing itself — where a bool that was computed per lane and is also needed as a
+// mask pays a vote (wave_ballot of a bool: two VALU operations), a mask that is also needed per lane pays nothing
+__device__ __forceinline__ bool lane_of(uint64_t m)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+#else
+    return (m & 1ull) != 0ull;
+#endif
+}
 // max(v, +0) for a non-NaN float as one integer max (negative floats are negative ints)
 __device__ __forceinline__ float clamp0(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
 

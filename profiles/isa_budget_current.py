@@ -9,8 +9,8 @@ Why: the tile kernel's frame time follows its resident waves (128 VGPRs and <= 9
 took the spill instructions 21 -> 44: DESIGN.md 5.2).  __graft_entry__.build() runs this after compiling, and
 tests/test_isa_lint.py asserts the limits, so that such a change fails at build time instead of at the bench.
 
-Per kernel: VGPRs, SGPRs, spilled VGPRs / SGPRs (registers), scratch bytes, LDS bytes, instructions, VALU / SALU instructions,
-spill instructions (scratch_*), v_readlane / v_writelane (SGPR spill traffic).  With --marks (a -DGRT_MARKS -S build of the
+Per kernel: VGPRs, SGPRs, spilled VGPRs / SGPRs (registers), scratch bytes, LDS bytes, instructions, VALU / SALU instructions
+(salu = branch + s_nop + s_waitcnt + salu_alu, each also on its own: tests/test_scalar_isa.py), spill instructions (scratch_*), v_readlane / v_writelane (SGPR spill traffic).  With --marks (a -DGRT_MARKS -S build of the
 tile kernel): the same static counts of the camera-ray kernel per marked section of its source."""
 import glob
 import json
@@ -36,7 +36,7 @@ def demangle(names):
 def instr_stats(lines):
     """(the assembly printer says for every machine basic block which loop it is in: `.LBBx_y: ; in Loop: Header=… Depth=N`)"""
     c = {"instructions": 0, "valu": 0, "salu": 0, "spill_instructions": 0, "spill_instructions_in_loops": 0, "lane_moves": 0,
-         "lane_moves_in_loops": 0, "lds": 0, "vmem": 0, "smem": 0}
+         "lane_moves_in_loops": 0, "lds": 0, "vmem": 0, "smem": 0, "branch": 0, "s_nop": 0, "s_waitcnt": 0, "salu_alu": 0}
     depth = 0
     for l in lines:
         m = re.match(r"^\.LBB\d+_\d+:(.*)$", l)
@@ -56,7 +56,10 @@ def instr_stats(lines):
         elif op.startswith(("s_load", "s_buffer_load")):
             c["smem"] += 1
         elif op.startswith("s_"):
-            c["salu"] += 1
+            c["salu"] += 1  # everything the scalar unit issues; its parts: branches, s_nop, s_waitcnt, and the rest (salu_alu)
+            k = ("branch" if op.startswith(("s_cbranch", "s_branch")) else "s_nop" if op == "s_nop" else
+                 "s_waitcnt" if op.startswith("s_waitcnt") else "salu_alu")
+            c[k] += 1
         elif op.startswith("scratch_"):
             c["spill_instructions"] += 1
             c["spill_instructions_in_loops"] += 1 if depth else 0
