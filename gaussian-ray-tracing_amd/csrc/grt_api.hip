@@ -564,6 +564,8 @@ static void free_slot_state(grt_ctx* c)
     (void)hipFree(c->d_bverdict); (void)hipFree(c->d_qunit); (void)hipFree(c->d_qskip); (void)hipFree(c->d_heavy_a);
     reap_old_pools(c, true, nullptr);
     (void)hipFree(c->d_ovf); (void)hipFree(c->d_ovf_next);
+    (void)hipFree(c->d_gacc); (void)hipFree(c->d_gacc_sh);
+    if (c->ev_bwd) (void)hipEventDestroy(c->ev_bwd);
     (void)hipFree(c->d_err);
     if (c->h_ovf_used) (void)hipHostFree(c->h_ovf_used);
     if (c->h_err) (void)hipHostFree(c->h_err);
@@ -670,6 +672,7 @@ int grt_set_option(grt_ctx* c, int option, int value)
     else if (option == GRT_OPT_QUAD_PARTS) { c->opt_quad_parts = std::max(0, value); c->cost_valid = false; c->order_ready = false; } // (2: whatever the launch's size; > 2: and that many parts at most — testing)
     else if (option == GRT_OPT_TILE_PARTS_LOAD_PCT) { c->opt_tile_parts_load_pct = std::min(100000, std::max(0, value)); c->cost_valid = false; c->order_ready = false; }
     else if (option == GRT_OPT_TILE_PRIO_DIV) { c->opt_tile_prio = std::max(0, value); }
+    else if (option == GRT_OPT_BWD_PLAIN_ATOMICS) { c->opt_bwd_plain = value ? 1 : 0; }
     else if (option == GRT_OPT_TILE_RESERVE) { c->opt_tile_reserve = std::min(63, std::max(-1, value)); }
     else if (option == GRT_OPT_LEAF_MAX) {
         if (value < 1 || value > (int)kLeafMaxPrims) { c->err = "GRT_OPT_LEAF_MAX must be 1..8"; return GRT_ERR_INVALID; }
@@ -1128,6 +1131,7 @@ int grt_get_memory_info(const grt_ctx* c, grt_memory_info* o)
     v += (uint64_t)c->ovf_chunks * kTileOvfChunkBytes;
     v += (uint64_t)c->cost_cap * 12;
     v += (uint64_t)c->wf_cap * (48 + 128 + 4 + 64);
+    v += (uint64_t)c->gacc_cap * 64 + (uint64_t)c->gacc_sh_cap * 180; // backward pass: gradient rows, higher-SH buffer
     o->slot_bytes = v;
     o->overflow_pool_bytes = (uint64_t)c->ovf_chunks * kTileOvfChunkBytes;
     o->overflow_chunks = c->ovf_chunks;

@@ -414,4 +414,12 @@ struct grt_ctx {
     // big-window kernel for the heaviest blocks: 0 off, 1 on, 2 auto = on for small launches (<= 3072 blocks: a
     // multi-GPU rank's share of a 1080p frame), where the heaviest tile and not throughput bounds the frame
     int opt_heavy_split = 2;
+    // backward pass (grt_backward.hip): the slot's gradient buffers — one 64-B row per particle, and the 45 higher SH floats of
+    // degree >= 1 frames — zero between calls (the flush kernel that adds them into the caller's arrays zeroes them)
+    float *d_gacc = nullptr, *d_gacc_sh = nullptr;
+    uint64_t gacc_cap = 0, gacc_sh_cap = 0; // particles they hold
+    hipEvent_t ev_bwd = nullptr;            // behind the last backward's flush
+    bool bwd_pending = false;
+    hipStream_t bwd_stream = nullptr;
+    int opt_bwd_plain = 0;                  // GRT_OPT_BWD_PLAIN_ATOMICS
 };

@@ -61,6 +61,14 @@ class Gaussians(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "sh")]
 
 
+class GaussianGrads(C.Structure):
+    """grt_gaussian_grads (include/grt.h): device pointers of the gradient arrays by original particle id, each may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "sh")]
+
+
+GRAD_SHAPES = {"pos": (3,), "scale": (3,), "quat": (4,), "opacity": (), "sh": (16, 3)}
+
+
 class Mesh(C.Structure):
     _fields_ = [("verts", C.c_void_p), ("normals", C.c_void_p), ("nv", C.c_uint32), ("faces", C.c_void_p),
                 ("nf", C.c_uint32)]
@@ -82,13 +90,14 @@ OPT_BVH_ROTATIONS = 35
 OPT_BUNDLE_PREDICT = 36
 OPT_MESH_PRIMARY_WAVE = 37
 OPT_SPLIT_VOL_PCT = 38
+OPT_BWD_PLAIN_ATOMICS = 39
 ERR_LIMIT = -5
 KERNEL_AUTO, KERNEL_PERLANE, KERNEL_WAVE, KERNEL_STREAM, KERNEL_STREAM_BIG, KERNEL_TILE = 0, 1, 2, 3, 4, 5
 
 EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
-    "grt_render_rays_aux", "grt_sync",
+    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -134,6 +143,8 @@ def lib():
         L.grt_render_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp]
         L.grt_render_aux.argtypes = [vp, C.POINTER(Params), vp, vp, C.POINTER(AuxOut), u32, u32, u32, u32, vp]
         L.grt_render_rays_aux.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(AuxOut), vp]
+        L.grt_backward.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
+        L.grt_backward_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -318,6 +329,8 @@ class Tracer:
         self.device = device if scene is None else scene.device
         self._h = C.c_void_p()
         self._scene = scene  # keeps the parent alive as long as the view
+        self.n_particles = 0  # of the last upload
+        self.n_uploads = 0    # uploads so far (grt_torch: a backward refuses a scene that is no longer its forward's)
         rc = lib().grt_create(C.byref(self._h), device) if scene is None else lib().grt_create_view(scene._h, C.byref(self._h))
         if rc != 0:
             raise GrtError(f"grt_create failed ({rc}): {lib().grt_last_error(None).decode()}")
@@ -345,6 +358,8 @@ class Tracer:
 
     def upload(self, acts, alpha_min=0.01):
         a = {k: np.ascontiguousarray(v, np.float32) for k, v in acts.items()}
+        self.n_particles = len(a["pos"])
+        self.n_uploads += 1
         g = Gaussians(*(a[k].ctypes.data for k in ("pos", "scale", "quat", "opacity", "sh")))
         self._check(lib().grt_upload_gaussians(self._h, C.byref(g), len(a["pos"])))
         self._check(lib().grt_build_bvh(self._h, alpha_min))
@@ -472,6 +487,38 @@ class Tracer:
         self._check(lib().grt_render_rays_aux(self._h, C.byref(params), rays.data_ptr(), n,
                                               out["f32"].data_ptr() if want_f32 else None, C.byref(ptrs), self._stream()))
         return out
+
+    def _grad_buffers(self, into, groups, dev):
+        """The gradient tensors of a backward call: `into` (accumulated into; its keys are the groups computed) or zeroed ones for
+        `groups` (default: all five)."""
+        t = self._torch
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if into is None:
+            into = {k: t.zeros((n,) + GRAD_SHAPES[k], dtype=t.float32, device=dev) for k in (groups or GRAD_SHAPES)}
+        for k, v in into.items():
+            if k not in GRAD_SHAPES or tuple(v.shape) != (n,) + GRAD_SHAPES[k] or v.dtype != t.float32 or not v.is_contiguous():
+                raise GrtError(f"backward: gradient tensor '{k}' must be contiguous float32 of shape {(n,) + GRAD_SHAPES[k]}")
+        return into, GaussianGrads(*(into[k].data_ptr() if k in into else None for k in ("pos", "scale", "quat", "opacity", "sh")))
+
+    def backward(self, params, rgbf, alpha, grad_rgbf, grad_alpha=None, window=None, into=None, groups=None):
+        """grt_backward: gradients of a loss on the frame (rgbf [h][w][3], alpha [h][w] as render_aux wrote them; grad_rgbf / grad_alpha
+        the loss's gradients with respect to them) with respect to the uploaded Gaussians -> dict of torch tensors pos, scale, quat,
+        opacity, sh (allocated zeroed, or accumulated into `into`).  Not bitwise reproducible (float atomics); include/grt.h."""
+        dev = f"cuda:{self.device}"
+        into, ptrs = self._grad_buffers(into, groups, dev)
+        x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
+        keep = [x.contiguous() if x is not None else None for x in (rgbf, alpha, grad_rgbf, grad_alpha)]
+        self._check(lib().grt_backward(self._h, C.byref(params), *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs),
+                                       x0, y0, x1, y1, self._stream()))
+        return into
+
+    def backward_rays(self, params, rays, rgbf, alpha, grad_rgbf, grad_alpha=None, into=None, groups=None):
+        """grt_backward_rays: as backward() for rays [n][6] (device, float32 o, d); rgbf [n][3], alpha [n] as render_rays_aux wrote them."""
+        into, ptrs = self._grad_buffers(into, groups, rays.device)
+        keep = [x.contiguous() if x is not None else None for x in (rgbf, alpha, grad_rgbf, grad_alpha)]
+        self._check(lib().grt_backward_rays(self._h, C.byref(params), rays.data_ptr(), rays.shape[0],
+                                            *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs), self._stream()))
+        return into
 
     def counters(self):
         c = Counters()

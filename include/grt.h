@@ -125,7 +125,8 @@ typedef struct {
 
 typedef struct {
     uint64_t scene_bytes;         /* device memory of the scene this context renders (shared by a context and its views) */
-    uint64_t slot_bytes;          /* device memory of this frame slot: eye records, overflow pool, feedback, wavefront queues */
+    uint64_t slot_bytes;          /* device memory of this frame slot: eye records, overflow pool, feedback, wavefront queues,
+                                     the backward pass's gradient buffers */
     uint64_t overflow_pool_bytes; /* of which: the tile kernel's pool of window-overflow bags */
     uint32_t overflow_chunks;     /* chunks (32 KiB: 32 entries x 64 rays; a tile takes up to three) in that pool */
     uint32_t overflow_demand;     /* the demand the pool follows: median of what the last eight frames read back asked for */
@@ -241,7 +242,10 @@ enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_count
                                            bit */,
        GRT_OPT_SPLIT_VOL_PCT = 38       /* spatial splits: a proxy longer than the piece length is cut when the boxes of its cells together hold
                                            less than value % of its own box's volume (default 400: practically always; rounds 3-5: 50).  Per context;
-                                           next build.  Same pixels */ };
+                                           next build.  Same pixels */,
+       GRT_OPT_BWD_PLAIN_ATOMICS = 39   /* (testing) backward pass: 1 = every lane adds its own 14 values per event to its particle's row of the
+                                           gradient buffer; 0 (default): lanes of a wave that composite the same particle in the same slot
+                                           of their k-buffers reduce over the wave first.  Same gradients within the float32 tolerance */ };
 
 /* ---- context ---- */
 GRT_API int grt_create(grt_ctx** out, int device);
@@ -334,6 +338,55 @@ GRT_API int grt_render_aux(grt_ctx* ctx, const grt_params* p, uint8_t* d_rgb8, f
                            uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_render_rays_aux(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, float* d_rgbf,
                                 const grt_aux_out* aux, void* stream);
+/* ---- backward pass: gradients of a loss on the frame with respect to the Gaussians (Gaussian-only frames) ----
+ * The function that is differentiated is what a ray without meshes renders (shaders/tracer.cu:68-82, 101; trace(),
+ * shaders/tracer.cuh:328-373):
+ *     rad   = sum_i T_i alpha_i L_i        T_1 = 1, T_{i+1} = T_i (1 - alpha_i)
+ *     A     = clamp(1 - T_end, 0, 1)       (grt_aux_out::alpha)
+ *     rgbf  = rad * A                      (the frame's colour is radiance TIMES density: directLight = rad * alpha)
+ * over the k-buffer's events i in key order (t, id, entry < exit): BOTH the entry and the exit event of a proxy are composited, with
+ * the same alpha; repeats of a split particle's pieces are dropped; an event counts when alpha_min < alpha_i, where
+ *     alpha_i = min(0.99, opacity r),  r = exp(-1/2 |p_g|^2),  p_g = A (mu - o - d_val d),  d_val = -(o_g.d_g) / max(1e-6, d_g.d_g),
+ *     o_g = A (o - mu),  d_g = A d,  A = diag(1/s) R^T,  R = glm::mat3_cast(q) of the quaternion AS UPLOADED (no normalisation inside),
+ *     L_i = max(0, 0.5 + sum_k Y_k(d/|d|) sh_k)  over the k < (sh_degree_max + 1)^2.
+ * It is differentiated WITH ITS DISCRETE DECISIONS HELD FIXED: which events exist and their order, alpha_min < alpha, the 0.99 clamp
+ * (zero gradient into opacity and geometry where it binds), max(L, 0) per channel (zero gradient into SH where it binds),
+ * max(1e-6, .) (the denominator a constant where it binds; d_val minimises |p_g|^2, so p_g is differentiated at fixed d_val), where
+ * the ray stops (T > minTransmittance).  With g_C = dloss/drgbf, g_A = dloss/dalpha (NULL = 0), g_rad = A g_C,
+ * g_A' = g_A + g_C.rad, S_i = sum_{j>i} T_j alpha_j L_j:
+ *     dloss/dalpha_i = g_rad.(T_i L_i - S_i / (1 - alpha_i)) + g_A' T_end / (1 - alpha_i)
+ *     dloss/dL_i     = T_i alpha_i g_rad  (per channel, where L_i > 0)                      -> sh_k += Y_k * that
+ *     dalpha_i/dopacity = r,  dalpha_i/dr = opacity  (when opacity r < 0.99);  dr/dp_g = -r p_g;  with v = mu - (o + d_val d), p_g = A v:
+ *     d/dmu = A^T g_p,   d/ds_k = -g_p,k (R^T v)_k / s_k^2,   d/dR_jk = v_j g_p,k / s_k -> q through mat3_cast.
+ * Gradients are with respect to the ACTIVATED attributes of grt_gaussians; the chain through exp / sigmoid / normalise is the
+ * caller's.  Gradients with respect to rays / camera, and upstream gradients of depth / count, are not computed.
+ *   d_rgbf, d_alpha          what the forward call wrote for the same parameters and window (grt_render_aux: d_rgbf and aux.alpha);
+ *                            required.  (The kernel re-derives rad and T_end with a sweep of its own: DESIGN.md 5.8.)
+ *   d_grad_rgbf, d_grad_alpha  upstream gradients, laid out like d_rgbf / alpha; d_grad_alpha may be NULL (= 0).
+ *   grads                    device arrays by ORIGINAL particle id like grt_gaussians: [n][3] [n][3] [n][4] [n] [n][16][3]; each may be
+ *                            NULL (that group is not computed).  The gradients are ADDED to what the arrays hold: the caller zeroes them.
+ * Fisheye pixels with r > 1 and pixels outside the window contribute nothing; so do rays the raygen loop does not trace
+ * (|d| <= 0.1, max_bounces = 0).  Asynchronous on `stream` like grt_render; grt_last_kernel_ms reports the backward's device time.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error; the context stays usable): meshes set (the backward of mesh frames is future
+ * work), GRT_OPT_COUNTERS = 1, no BVH, a NULL required pointer.  The sums are float atomics whose order of arrival differs from call
+ * to call: gradients are NOT bitwise reproducible between calls (tests compare within a tolerance measured for float32 evaluation).
+ * A frame rendered after a backward is bit-identical to one rendered before it.  Backward calls of one context share its gradient
+ * buffer: a call on another stream than the last one's waits for that one.  The buffer — 64 B per particle, and 180 B more per
+ * particle once a backward at SH degree >= 1 has run (244 MB at a million particles) — is allocated by the first backward and kept
+ * until the context is destroyed; grt_memory_info::slot_bytes counts it. */
+typedef struct {
+    float* pos;
+    float* scale;
+    float* quat;
+    float* opacity;
+    float* sh;
+} grt_gaussian_grads;
+GRT_API int grt_backward(grt_ctx* ctx, const grt_params* p, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf,
+                         const float* d_grad_alpha, const grt_gaussian_grads* grads, uint32_t x0, uint32_t y0, uint32_t x1,
+                         uint32_t y1, void* stream);
+GRT_API int grt_backward_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_rgbf,
+                              const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,
+                              const grt_gaussian_grads* grads, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
