@@ -22,8 +22,17 @@ TOL is measured, not chosen (measure_f32(); tests/test_grad_check.py runs and pr
 sequential order, and once more with the events scattered in reverse order) against the float64 values, as error / scale, maximum
 over all parameters of all scenes of tests/test_gpu_grad.py; TOL = 4 x that maximum (the GPU may associate differently, its expf
 differs from glibc's in the last bit and its atomics arrive in any order).
+
+4. evaluate_chunked(): 1-3 for a frame too large for one call.  Gradients and scales are sums over rays, so the frame is cut into
+   chunks of rays, each chunk walked, silenced and evaluated on its own by fresh worker processes (this file run as a script: numpy,
+   oracle and grad_check only — never torch, never the GPU), and the chunks are added in float64.
 """
 import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+import time
 
 import numpy as np
 
@@ -42,6 +51,21 @@ FAULTS = ("exit_dropped", "clamp_ignored", "density_factor_left_out", "sign_flip
 MEASURED_F32 = {"pinhole_deg0": 1.84e-5, "sh3": 8.16e-6, "fisheye": 5.05e-6, "needles": 2.54e-4, "rays": 5.95e-6}
 MEASURED_F32_MAX = max(MEASURED_F32.values())
 TOL = 4 * MEASURED_F32_MAX  # the one constant every GPU comparison holds; a scene's own 4 x MEASURED_F32[scene] is asserted as well
+# The same figure for the scenes of grad_scenes.EDGE_NAMES and SIZE_NAMES, each measured on its own walk (tests/test_grad_check.py
+# measures the edge scenes' again on any machine, tests/test_gpu_grad_edges.py / test_gpu_grad_size.py every one on the walk they
+# hold; each asserts (figure / 2, figure]).  These do NOT enter TOL: a scene of this dict is held to 4 x its OWN figure (the same
+# margin), so the large scenes' small scales (C3: 1 M particles, few events each) loosen nothing for anyone else.  C2_whole is the
+# chunked checker's figure at chunks of 16 rows (20 480 rays): float32 within a chunk, the chunks added in float64.
+MEASURED_F32_MORE = {"inside": 2.36e-6, "cuts": 6.1e-6, "crowded": 5.1e-6, "ragged_rays": 7.35e-6,
+                     "C2_whole": 2.96e-5, "C3_sampled": 2.70e-4, "C3b_sampled": 2.75e-3, "C3_sh3_sampled": 5.10e-4}
+CHUNK_C2 = 16 * 1280    # rays per chunk of the C2 whole-frame check: the figure above belongs to this chunking
+
+
+def tol_of(name):
+    """The tolerance of a scene of MEASURED_F32_MORE: 4 x its own float32 figure."""
+    return 4 * MEASURED_F32_MORE[name]
+
+
 FRAGILE_REL = 1e-4      # a ray whose closest decision lies within this of its threshold is silenced (upstream set to 0), never excused
 MAX_SILENCED = 0.01     # ... and at most this fraction of a frame's rays may be
 
@@ -394,3 +418,102 @@ def measure_f32(parts, ev, rays, deg, gC, gA):
         for k, v in error_over_scale(got, want, scale).items():
             out[k] = max(out[k], v)
     return out
+
+
+# ---- whole large frames: chunks of rays over fresh worker processes ----
+def _chunk_worker(job_path, k):
+    """Worker k of a job: chunks k, k + workers, ... of the job's rays; writes <job>.out<k>.npz."""
+    job = np.load(job_path)
+    op = O.Params.from_buffer_copy(job["op"].tobytes())
+    parts, rays, live, gC, gA = job["parts"], job["rays"], job["live"], job["gC"], job["gA"]
+    chunk, workers, measure = int(job["chunk"]), int(job["workers"]), bool(job["measure"])
+    deg = op.sh_degree_max
+    sc = O.Scene(parts, float(job["alpha_min"]))
+    out = {}
+
+    def add(key, d):
+        for g_, v in d.items():
+            out[key + g_] = out.get(key + g_, 0.0) + np.asarray(v, np.float64)
+
+    events = 0
+    frag_all = []
+    t_walk = t_eval = 0.0
+    for c0 in range(k * chunk, len(rays), workers * chunk):
+        sl = slice(c0, min(c0 + chunk, len(rays)))
+        t0 = time.perf_counter()
+        ev = walk(parts, op, sc, rays[sl], live[sl])
+        t1 = time.perf_counter()
+        c, a, _ = silence(ev, gC[sl], gA[sl])
+        frag_all.append(c0 + np.nonzero((ev.margin < FRAGILE_REL) & live[sl])[0])
+        events += len(ev.ray)
+        want, scale = evaluate(parts, ev, rays[sl], deg, c, a)
+        add("want_", want); add("scale_", scale)
+        if measure:
+            for rev in (False, True):
+                add("f32r_" if rev else "f32f_", evaluate(parts, ev, rays[sl], deg, c, a, dt=f32, reverse=rev)[0])
+        t_walk += t1 - t0; t_eval += time.perf_counter() - t1
+    sc.close()
+    if not out:  # (more workers than chunks)
+        shapes = evaluate(parts, Events([], [], [], [], np.ones(0), 0), rays[:0], deg, gC[:0], gA[:0])[0]
+        for key in ("want_", "scale_") + (("f32f_", "f32r_") if measure else ()):
+            add(key, {g_: np.zeros(v.shape) for g_, v in shapes.items()})
+    np.savez(f"{job_path}.out{k}.npz", events=events, fragile=np.concatenate(frag_all) if frag_all else np.zeros(0, np.int64),
+             t_walk=t_walk, t_eval=t_eval, modules=np.array(sorted(m for m in sys.modules if "." not in m)), **out)
+
+
+def evaluate_chunked(parts, op, rays, live, gC, gA, chunk, workers, alpha_min=0.01, measure=True, tmp_dir=None):
+    """walk + silence + evaluate (and, measure: the float32 evaluation in both scatter orders) over chunks of `chunk` rays on `workers`
+    fresh processes, each with an oracle Scene of its own, the chunks added in float64.  Returns a dict: want, scale (by group),
+    f32 (error / scale by group of the float32 evaluation — float32 inside a chunk, the chunks added in float64 —, None without
+    measure), events, silenced (rays), gC, gA (the upstream with the fragile rays silenced), seconds, walk_seconds, eval_seconds (summed
+    over the workers), modules (the top-level modules the workers had imported)."""
+    t0 = time.perf_counter()
+    parts = np.ascontiguousarray(parts, dtype=O.PARTICLE_DTYPE)
+    rays = np.ascontiguousarray(rays, f32).reshape(-1, 6)
+    n = len(rays)
+    live = np.ones(n, bool) if live is None else np.asarray(live, bool).reshape(-1)
+    gC = np.ascontiguousarray(gC).reshape(n, 3); gA = np.ascontiguousarray(gA).reshape(n)
+    workers = max(1, int(workers))
+    env = dict(os.environ)
+    here = os.path.dirname(os.path.abspath(__file__))
+    env["PYTHONPATH"] = os.pathsep.join([here, os.path.dirname(os.path.abspath(O.__file__))] + [x for x in [env.get("PYTHONPATH")] if x])
+    for v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
+        env[v] = "1"  # one thread per worker: the workers are the parallelism
+    with tempfile.TemporaryDirectory(dir=tmp_dir) as td:
+        job = os.path.join(td, "job.npz")
+        np.savez(job, parts=parts, op=np.frombuffer(bytes(op), np.uint8), rays=rays, live=live, gC=gC, gA=gA, chunk=chunk,
+                 workers=workers, measure=measure, alpha_min=alpha_min)
+        cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.abspath(__file__), "--chunk-worker", job]
+        procs = [subprocess.Popen(cmd + [str(k)], env=env, stdin=subprocess.DEVNULL) for k in range(workers)]
+        codes = [p.wait() for p in procs]
+        if any(codes):
+            raise CheckerMismatch(f"chunk workers ended with {codes}")
+        tot = {}
+        events, frag, t_walk, t_eval, modules = 0, [], 0.0, 0.0, set()
+        for k in range(workers):
+            r = np.load(f"{job}.out{k}.npz")
+            for key in r.files:
+                if key.split("_")[0] in ("want", "scale", "f32f", "f32r"):
+                    tot[key] = tot.get(key, 0.0) + r[key]
+            events += int(r["events"]); frag.append(r["fragile"]); t_walk += float(r["t_walk"]); t_eval += float(r["t_eval"])
+            modules |= set(r["modules"].tolist())
+    frag = np.concatenate(frag).astype(np.int64)
+    gCs = np.array(gC, copy=True); gAs = np.array(gA, copy=True)
+    gCs[frag] = 0; gAs[frag] = 0
+    want = {g_: tot["want_" + g_] for g_ in GROUPS}
+    scale = {g_: tot["scale_" + g_] for g_ in GROUPS}
+    m32 = None
+    if measure:
+        m32 = {g_: 0.0 for g_ in GROUPS}
+        for key in ("f32f_", "f32r_"):
+            for g_, v in error_over_scale({g_: tot[key + g_] for g_ in GROUPS}, want, scale).items():
+                m32[g_] = max(m32[g_], v)
+    return dict(want=want, scale=scale, f32=m32, events=events, silenced=len(frag), gC=gCs, gA=gAs, seconds=time.perf_counter() - t0,
+                walk_seconds=t_walk, eval_seconds=t_eval, modules=sorted(modules))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--chunk-worker":
+        _chunk_worker(sys.argv[2], int(sys.argv[3]))
+    else:
+        sys.exit("usage: grad_check.py --chunk-worker JOB.npz K (started by evaluate_chunked)")
