@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <hip/hip_runtime.h>
+#include <omp.h>
 #include <cstdio>
 #include <cstdlib>
 
@@ -178,6 +179,31 @@ __global__ void k_piece_counts(const float* __restrict__ scale, const float* __r
     counts[i] = g.p[0] * g.p[1] * g.p[2];
 }
 
+// world box of cell kk of the p[0] x p[1] x p[2] grid over particle i's proxy-local box, clipped to the proxy's own box l .. h
+// (k_piece_boxes at the build; k_refit_prim_boxes when the particle has moved: the cell stays, its box follows)
+__device__ __forceinline__ void piece_cell_box(const float* __restrict__ pos, const float* __restrict__ scale, const float* __restrict__ quat,
+                                               float s, uint32_t i, const uint32_t kk[3], const uint32_t p[3], float4 l, float4 h,
+                                               float bl[3], float bh[3])
+{
+    float Rg[9];
+    mat3_cast(quat[i * 4], quat[i * 4 + 1], quat[i * 4 + 2], quat[i * 4 + 3], Rg);
+    float mid[3], half[3];
+    for (int r = 0; r < 3; r++) {
+        const float e = scale[i * 3 + r] * s * kIcoTT, w = 2.0f * e / (float)p[r];
+        mid[r] = -e + ((float)kk[r] + 0.5f) * w;
+        half[r] = 0.5f * w * (1.0f + 1e-5f) + 1e-6f * e; // the cells overlap by a hair: no point of the proxy falls between two
+    }
+    const float L[3] = {l.x, l.y, l.z}, H[3] = {h.x, h.y, h.z};
+    for (int k = 0; k < 3; k++) {
+        float c = pos[i * 3 + k], hw = 0.0f;
+        for (int r = 0; r < 3; r++) { c += Rg[r * 3 + k] * mid[r]; hw += fabsf(Rg[r * 3 + k]) * half[r]; }
+        const float m = 2e-5f * (1.0f + fabsf(c) + hw); // rounding of the nine products above, and then some
+        bl[k] = fmaxf(c - hw - m, L[k]);
+        bh[k] = fminf(c + hw + m, H[k]);
+        if (!(bl[k] <= bh[k])) { bl[k] = L[k]; bh[k] = H[k]; } // (cannot happen: the cell meets the proxy's box)
+    }
+}
+
 // one thread per piece: its owner by binary search in the offsets, its cell, its box
 __global__ void k_piece_boxes(const float* __restrict__ pos, const float* __restrict__ scale, const float* __restrict__ quat,
                               const float* __restrict__ s_arr, const float4* __restrict__ lo, const float4* __restrict__ hi,
@@ -203,25 +229,8 @@ __global__ void k_piece_boxes(const float* __restrict__ pos, const float* __rest
     const uint32_t k1 = q % g.p[1], k2 = q / g.p[1];
     const uint32_t kk[3] = {k0, k1, k2};
     desc[j] = piece_desc(kk, g.p);
-    const float s = s_arr[i];
-    float Rg[9];
-    mat3_cast(quat[i * 4], quat[i * 4 + 1], quat[i * 4 + 2], quat[i * 4 + 3], Rg);
-    float mid[3], half[3];
-    for (int r = 0; r < 3; r++) {
-        const float e = scale[i * 3 + r] * s * kIcoTT, w = 2.0f * e / (float)g.p[r];
-        mid[r] = -e + ((float)kk[r] + 0.5f) * w;
-        half[r] = 0.5f * w * (1.0f + 1e-5f) + 1e-6f * e; // the cells overlap by a hair: no point of the proxy falls between two
-    }
     float bl[3], bh[3];
-    const float L[3] = {l.x, l.y, l.z}, H[3] = {h.x, h.y, h.z};
-    for (int k = 0; k < 3; k++) {
-        float c = pos[i * 3 + k], hw = 0.0f;
-        for (int r = 0; r < 3; r++) { c += Rg[r * 3 + k] * mid[r]; hw += fabsf(Rg[r * 3 + k]) * half[r]; }
-        const float m = 2e-5f * (1.0f + fabsf(c) + hw); // rounding of the nine products above, and then some
-        bl[k] = fmaxf(c - hw - m, L[k]);
-        bh[k] = fminf(c + hw + m, H[k]);
-        if (!(bl[k] <= bh[k])) { bl[k] = L[k]; bh[k] = H[k]; } // (cannot happen: the cell meets the proxy's box)
-    }
+    piece_cell_box(pos, scale, quat, s_arr[i], i, kk, g.p, l, h, bl, bh);
     plo[j] = make_float4(bl[0], bl[1], bl[2], 0.0f);
     phi[j] = make_float4(bh[0], bh[1], bh[2], INFINITY); // (a cell has no bounding sphere worth testing: see k_proxy_boxes)
 }
@@ -257,6 +266,24 @@ __global__ void k_log_diag_partial(const float4* __restrict__ lo, const float4* 
 // A = diag(1/scale) * R^T exactly as computeResponse forms it per hit (shaders/tracer.cuh:191-201).
 // (owner / desc: piece -> particle and the piece's cell (piece_desc) when large proxies were split, else nullptr:
 //  primitive = particle; the last word of the record is the cell descriptor, 0 for a whole proxy)
+__device__ __forceinline__ void write_record(const float* __restrict__ pos, const float* __restrict__ scale, const float* __restrict__ quat,
+                                             const float* __restrict__ opacity, const float* __restrict__ s_arr, uint32_t i, uint32_t cd,
+                                             float4* rec)
+{
+    float Rg[9];
+    mat3_cast(quat[i * 4], quat[i * 4 + 1], quat[i * 4 + 2], quat[i * 4 + 3], Rg);
+    float A[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const float inv = 1.0f / scale[i * 3 + r];
+#pragma unroll
+        for (int c = 0; c < 3; c++) A[r * 3 + c] = inv * Rg[r * 3 + c];
+    }
+    rec[0] = make_float4(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2], s_arr[i]);
+    rec[1] = make_float4(A[0], A[1], A[2], opacity[i]);
+    rec[2] = make_float4(A[3], A[4], A[5], __uint_as_float(i));
+    rec[3] = make_float4(A[6], A[7], A[8], __uint_as_float(cd));
+}
 __global__ void k_gather_records(const float* __restrict__ pos, const float* __restrict__ scale,
                                  const float* __restrict__ quat, const float* __restrict__ opacity,
                                  const float* __restrict__ s_arr, const uint32_t* __restrict__ order,
@@ -267,19 +294,59 @@ __global__ void k_gather_records(const float* __restrict__ pos, const float* __r
     if (j >= m) return;
     const uint32_t i = owner ? owner[order[j]] : order[j];
     const uint32_t cd = desc ? desc[order[j]] : 0u;
-    float Rg[9];
-    mat3_cast(quat[i * 4], quat[i * 4 + 1], quat[i * 4 + 2], quat[i * 4 + 3], Rg);
-    float A[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float inv = 1.0f / scale[i * 3 + r];
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[r * 3 + c] = inv * Rg[r * 3 + c];
-    }
-    rec[(size_t)j * 4 + 0] = make_float4(pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2], s_arr[i]);
-    rec[(size_t)j * 4 + 1] = make_float4(A[0], A[1], A[2], opacity[i]);
-    rec[(size_t)j * 4 + 2] = make_float4(A[3], A[4], A[5], __uint_as_float(i));
-    rec[(size_t)j * 4 + 3] = make_float4(A[6], A[7], A[8], __uint_as_float(cd));
+    write_record(pos, scale, quat, opacity, s_arr, i, cd, rec + (size_t)j * 4);
+}
+
+// ---- refit (grt_update_gaussians_device): the tree in hand keeps its sorted order; a sorted primitive's particle and
+// cell are read from its OLD record (the id bits and the cell descriptor, which a refit never changes) ----
+// boxes of the sorted primitives from the particles' new values: a whole proxy takes its new box (lo / hi by particle: k_proxy_boxes),
+// a piece the new box of its old cell
+__global__ void k_refit_prim_boxes(const float4* __restrict__ rec, const float* __restrict__ pos, const float* __restrict__ scale,
+                                   const float* __restrict__ quat, const float* __restrict__ s_arr, const float4* __restrict__ lo,
+                                   const float4* __restrict__ hi, uint32_t m, uint32_t n, float4* __restrict__ lb_lo, float4* __restrict__ lb_hi)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t i = min(__float_as_uint(rec[(size_t)j * 4 + 2].w), n - 1u); // (an id is < n: the clamp only keeps a damaged record in bounds)
+    const uint32_t cd = __float_as_uint(rec[(size_t)j * 4 + 3].w);
+    const float4 l = lo[i], h = hi[i];
+    if (cd == 0u) { lb_lo[j] = l; lb_hi[j] = h; return; }
+    uint32_t kk[3], p[3];
+    for (int r = 0; r < 3; r++) { kk[r] = (cd >> (10 * r)) & 31u; p[r] = ((cd >> (10 * r + 5)) & 31u) + 1u; } // (piece_desc, grt_device.h)
+    float bl[3], bh[3];
+    piece_cell_box(pos, scale, quat, s_arr[i], i, kk, p, l, h, bl, bh);
+    lb_lo[j] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+    lb_hi[j] = make_float4(bh[0], bh[1], bh[2], INFINITY);
+}
+
+// the records again, in place: each thread reads the two words it keeps before it writes its record
+__global__ void k_regather_records(const float* __restrict__ pos, const float* __restrict__ scale, const float* __restrict__ quat,
+                                   const float* __restrict__ opacity, const float* __restrict__ s_arr, uint32_t m, uint32_t n, float4* rec)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t i = min(__float_as_uint(rec[(size_t)j * 4 + 2].w), n - 1u);
+    const uint32_t cd = __float_as_uint(rec[(size_t)j * 4 + 3].w);
+    write_record(pos, scale, quat, opacity, s_arr, i, cd, rec + (size_t)j * 4);
+}
+
+// in_tree[i] = 1 for every particle a record names (in_tree zeroed before; the pieces of a particle all write the same byte)
+__global__ void k_mark_in_tree(const float4* __restrict__ rec, uint32_t m, uint32_t n, uint8_t* __restrict__ in_tree)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t i = __float_as_uint(rec[(size_t)j * 4 + 2].w);
+    if (i < n) in_tree[i] = 1u;
+}
+
+// does the set of particles with a valid new box (hittable and finite: k_proxy_boxes) differ from the set in the tree?
+__global__ void k_set_changed(const float4* __restrict__ lo, const float4* __restrict__ hi, const uint8_t* __restrict__ in_tree, uint32_t n,
+                              uint32_t* __restrict__ flag)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool valid = lo[i].x <= hi[i].x;
+    if (valid != (in_tree[i] != 0u)) atomicOr(flag, 1u);
 }
 
 // Eye records: everything in the proxy test that depends on the ray ORIGIN only.  Camera rays share one origin,
@@ -545,6 +612,19 @@ static void free_gaussians(grt_ctx* c)
     c->built = false;
 }
 
+// scratch of grt_update_gaussians_device
+static void free_update_scratch(grt_ctx* c)
+{
+    (void)hipFree(c->upd_s); (void)hipFree(c->upd_lo); (void)hipFree(c->upd_hi); (void)hipFree(c->upd_lb_lo); (void)hipFree(c->upd_lb_hi);
+    (void)hipFree(c->upd_in_tree); (void)hipFree(c->upd_flag); (void)hipFree(c->upd_part);
+    c->upd_s = nullptr; c->upd_lo = c->upd_hi = c->upd_lb_lo = c->upd_lb_hi = nullptr;
+    c->upd_in_tree = nullptr; c->upd_flag = nullptr; c->upd_part = nullptr;
+    c->upd_cap_n = c->upd_cap_m = 0;
+    if (c->ev_upd0) (void)hipEventDestroy(c->ev_upd0);
+    if (c->ev_upd1) (void)hipEventDestroy(c->ev_upd1);
+    c->ev_upd0 = c->ev_upd1 = nullptr;
+}
+
 static void free_meshes(grt_ctx* c)
 {
     (void)hipFree(c->d_tri); (void)hipFree(c->d_faces); (void)hipFree(c->d_vnormals);
@@ -584,6 +664,7 @@ static void destroy_now(grt_ctx* c)
 {
     if (!c->parent) {
         free_gaussians(c);
+        free_update_scratch(c);
         free_meshes(c);
         free_bvh(&c->gbvh);
         (void)hipFree(c->d_rec);
@@ -673,6 +754,7 @@ int grt_set_option(grt_ctx* c, int option, int value)
     else if (option == GRT_OPT_TILE_PARTS_LOAD_PCT) { c->opt_tile_parts_load_pct = std::min(100000, std::max(0, value)); c->cost_valid = false; c->order_ready = false; }
     else if (option == GRT_OPT_TILE_PRIO_DIV) { c->opt_tile_prio = std::max(0, value); }
     else if (option == GRT_OPT_BWD_PLAIN_ATOMICS) { c->opt_bwd_plain = value ? 1 : 0; }
+    else if (option == GRT_OPT_REFIT_MAX_AREA_PCT) { NOT_A_VIEW(c, "GRT_OPT_REFIT_MAX_AREA_PCT"); c->opt_refit_max_area_pct = std::max(0, value); }
     else if (option == GRT_OPT_TILE_RESERVE) { c->opt_tile_reserve = std::min(63, std::max(-1, value)); }
     else if (option == GRT_OPT_LEAF_MAX) {
         if (value < 1 || value > (int)kLeafMaxPrims) { c->err = "GRT_OPT_LEAF_MAX must be 1..8"; return GRT_ERR_INVALID; }
@@ -719,6 +801,7 @@ int grt_upload_gaussians(grt_ctx* c, const grt_gaussians* g, uint64_t n)
     return GRT_OK;
 }
 
+static int build_gaussian_bvh(grt_ctx* c, float alpha_min, const float* s);
 int grt_build_bvh(grt_ctx* c, float alpha_min)
 {
     if (c) c->scene_epoch++;
@@ -728,21 +811,33 @@ int grt_build_bvh(grt_ctx* c, float alpha_min)
     CHK(c, hipSetDevice(c->device));
     CHK(c, hipDeviceSynchronize());
     c->built = false;
+    const uint32_t n = (uint32_t)c->n;
+    // proxy half-width s = sqrtf(2 logf(opacity/alpha_min)) on the HOST, as the reference does
+    // (src/GaussianTracer.cpp:306) — keeps the libm-dependent value identical to the host libm's.
+    std::vector<float> s(n);
+    for (uint32_t i = 0; i < n; i++) s[i] = sqrtf(2.0f * logf(c->h_opacity[i] / alpha_min));
+    return build_gaussian_bvh(c, alpha_min, s.data());
+}
+
+// The Gaussian BVH and the proxy records from the attributes in device memory and the half-widths s [c->n] the host computed:
+// the body of grt_build_bvh, shared with grt_update_gaussians_device (the device is idle when this is called).
+static int build_gaussian_bvh(grt_ctx* c, float alpha_min, const float* s)
+{
+    c->built = false;
     c->alpha_min = alpha_min;
+    c->area_build = 0.0;
     const uint32_t n = (uint32_t)c->n;
     c->gbvh.n_prims = 0;
     c->gbvh.root_ref = kNoRoot;
     c->gbvh.height = 0;
     c->has_pieces = false;
+    c->built_opts[0] = c->opt_leaf_max; c->built_opts[1] = c->opt_size_classes; c->built_opts[2] = c->opt_split;
+    c->built_opts[3] = c->opt_split_vol_pct; c->built_opts[4] = c->opt_bvh_rotations;
     if (n == 0) { c->built = true; return GRT_OK; }
-    // proxy half-width s = sqrtf(2 logf(opacity/alpha_min)) on the HOST, as the reference does
-    // (src/GaussianTracer.cpp:306) — keeps the libm-dependent value identical to the host libm's.
-    std::vector<float> s(n);
-    for (uint32_t i = 0; i < n; i++) s[i] = sqrtf(2.0f * logf(c->h_opacity[i] / alpha_min));
+    hipError_t e;
     float* d_s = nullptr;
     float4 *d_lo = nullptr, *d_hi = nullptr;
     int rc = GRT_OK;
-    hipError_t e;
     if ((e = hipMalloc(&d_s, n * sizeof(float))) != hipSuccess || (e = hipMalloc(&d_lo, n * sizeof(float4))) != hipSuccess ||
         (e = hipMalloc(&d_hi, n * sizeof(float4))) != hipSuccess) {
         c->err = std::string("grt_build_bvh: hipMalloc: ") + hipGetErrorString(e);
@@ -755,7 +850,7 @@ int grt_build_bvh(grt_ctx* c, float alpha_min)
     c->n_hittable = 0;
     for (uint32_t i = 0; i < n; i++) c->n_hittable += (s[i] > 0.0f) ? 1u : 0u;
     if (rc == GRT_OK) {
-        (void)hipMemcpyAsync(d_s, s.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+        (void)hipMemcpyAsync(d_s, s, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
         (void)hipEventRecord(c->ev0, c->stream);
         hipLaunchKernelGGL(k_proxy_boxes, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_pos, c->d_scale, c->d_quat,
                            d_s, n, d_lo, d_hi);
@@ -876,6 +971,201 @@ int grt_build_bvh(grt_ctx* c, float alpha_min)
     c->erec_valid = false;
     if (rc == GRT_OK) { c->built = true; c->built_leaf_max = c->opt_leaf_max; c->has_pieces = have_pieces; }
     return rc;
+}
+
+// ---- device-resident scene update (include/grt.h) ----
+static int update_scratch_n(grt_ctx* c, uint64_t n)
+{
+    if (!c->ev_upd0) CHK(c, hipEventCreate(&c->ev_upd0));
+    if (!c->ev_upd1) CHK(c, hipEventCreate(&c->ev_upd1));
+    if (!c->upd_flag) CHK(c, hipMalloc(&c->upd_flag, sizeof(uint32_t)));
+    if (!c->upd_part) CHK(c, hipMalloc(&c->upd_part, kAreaParts * sizeof(double)));
+    if (c->upd_cap_n >= n) return GRT_OK;
+    (void)hipFree(c->upd_s); (void)hipFree(c->upd_lo); (void)hipFree(c->upd_hi); (void)hipFree(c->upd_in_tree);
+    c->upd_s = nullptr; c->upd_lo = c->upd_hi = nullptr; c->upd_in_tree = nullptr;
+    c->upd_cap_n = 0;
+    CHK(c, hipMalloc(&c->upd_s, n * sizeof(float)));
+    CHK(c, hipMalloc(&c->upd_lo, n * sizeof(float4)));
+    CHK(c, hipMalloc(&c->upd_hi, n * sizeof(float4)));
+    CHK(c, hipMalloc(&c->upd_in_tree, n));
+    c->upd_cap_n = n;
+    return GRT_OK;
+}
+static int update_scratch_m(grt_ctx* c, uint64_t m)
+{
+    if (c->upd_cap_m >= m) return GRT_OK;
+    (void)hipFree(c->upd_lb_lo); (void)hipFree(c->upd_lb_hi);
+    c->upd_lb_lo = c->upd_lb_hi = nullptr;
+    c->upd_cap_m = 0;
+    CHK(c, hipMalloc(&c->upd_lb_lo, m * sizeof(float4)));
+    CHK(c, hipMalloc(&c->upd_lb_hi, m * sizeof(float4)));
+    c->upd_cap_m = m;
+    return GRT_OK;
+}
+
+static const char* update_reason_text(uint32_t r)
+{
+    switch (r) {
+    case GRT_UPDATE_REASON_FIRST_BUILD: return "no Gaussian BVH has been built";
+    case GRT_UPDATE_REASON_N_CHANGED: return "the number of particles changed";
+    case GRT_UPDATE_REASON_SET_CHANGED: return "the set of hittable, finite particles is not the one in the tree";
+    case GRT_UPDATE_REASON_OPTION_CHANGED: return "a build option changed since the last build";
+    case GRT_UPDATE_REASON_AREA: return "the refitted boxes grew past GRT_OPT_REFIT_MAX_AREA_PCT";
+    default: return "none";
+    }
+}
+
+int grt_update_gaussians_device(grt_ctx* c, const grt_gaussians* g, uint64_t n, float alpha_min, int mode, void* stream, grt_update_info* out)
+{
+    (void)stream; // (the device is synchronised below: that orders the reads after the work queued on this stream, and on every other)
+    if (!c) return GRT_ERR_INVALID;
+    if (out) memset(out, 0, sizeof(*out));
+    if (mode != GRT_UPDATE_AUTO && mode != GRT_UPDATE_REFIT && mode != GRT_UPDATE_REBUILD) { c->err = "grt_update_gaussians_device: unknown mode"; return GRT_ERR_INVALID; }
+    if (!(alpha_min > 0.0f)) { c->err = "grt_update_gaussians_device: alpha_min must be > 0"; return GRT_ERR_INVALID; }
+    if (n && (!g || !g->pos || !g->scale || !g->quat || !g->opacity || !g->sh)) { c->err = "grt_update_gaussians_device: null argument"; return GRT_ERR_INVALID; }
+    if (n >= (1ull << 26)) { c->err = "grt_update_gaussians_device: more than 2^26-1 particles (hit keys carry a 26-bit id)"; return GRT_ERR_LIMIT; }
+    NOT_A_VIEW(c, "grt_update_gaussians_device");
+    CHK(c, hipSetDevice(c->device));
+    if (n) {
+        const void* ptrs[5] = {g->pos, g->scale, g->quat, g->opacity, g->sh};
+        static const char* const names[5] = {"pos", "scale", "quat", "opacity", "sh"};
+        for (int k = 0; k < 5; k++) {
+            hipPointerAttribute_t at;
+            memset(&at, 0, sizeof(at));
+            const hipError_t e = hipPointerGetAttributes(&at, ptrs[k]);
+            const bool dev_mem = e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) && at.device == c->device;
+            if (!dev_mem) {
+                (void)hipGetLastError(); // (an unregistered host pointer leaves an error behind)
+                c->err = std::string("grt_update_gaussians_device: ") + names[k] + " is not device memory of the context's GPU";
+                return GRT_ERR_INVALID;
+            }
+        }
+    }
+    CHK(c, hipDeviceSynchronize()); // the caller's stream; frames of this scene in flight on any stream (caller's, views')
+    const uint32_t nn = (uint32_t)n;
+    // ---- can the tree in hand be refitted? (the last condition, the set of particles in it, is decided on the device below) ----
+    uint32_t reason = GRT_UPDATE_REASON_NONE;
+    if (mode != GRT_UPDATE_REBUILD) {
+        if (!c->built) reason = GRT_UPDATE_REASON_FIRST_BUILD;
+        else if (n != c->n) reason = GRT_UPDATE_REASON_N_CHANGED;
+        else if (c->built_opts[0] != c->opt_leaf_max || c->built_opts[1] != c->opt_size_classes || c->built_opts[2] != c->opt_split ||
+                 c->built_opts[3] != c->opt_split_vol_pct || c->built_opts[4] != c->opt_bvh_rotations)
+            reason = GRT_UPDATE_REASON_OPTION_CHANGED;
+    }
+    bool try_refit = mode != GRT_UPDATE_REBUILD && reason == GRT_UPDATE_REASON_NONE;
+    uint32_t n_hit = 0;
+    if (n) {
+        int rc = update_scratch_n(c, n);
+        if (rc != GRT_OK) return rc;
+        // proxy half-width on the HOST, as grt_build_bvh computes it: the opacities come down, s goes up
+        c->upd_h_opacity.resize(n);
+        c->upd_h_s.resize(n);
+        CHK(c, hipMemcpy(c->upd_h_opacity.data(), g->opacity, n * sizeof(float), hipMemcpyDeviceToHost));
+        const float* op = c->upd_h_opacity.data();
+        float* hs = c->upd_h_s.data();
+        const int threads = n < 65536 ? 1 : std::max(1, std::min(16, omp_get_max_threads()));
+        long long hits = 0;
+        (void)threads;
+#pragma omp parallel for num_threads(threads) schedule(static) reduction(+ : hits)
+        for (long long i = 0; i < (long long)n; i++) {
+            hs[i] = sqrtf(2.0f * logf(op[i] / alpha_min));
+            hits += (hs[i] > 0.0f) ? 1 : 0;
+        }
+        n_hit = (uint32_t)hits;
+        CHK(c, hipMemcpyAsync(c->upd_s, hs, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        CHK(c, hipEventRecord(c->ev_upd0, c->stream));
+        if (try_refit) {
+            // the new proxy boxes, from the CALLER's arrays: nothing of the scene is touched before the refit is known to be possible
+            const uint32_t m = c->gbvh.n_prims;
+            uint32_t h_flag = 0;
+            hipLaunchKernelGGL(k_proxy_boxes, dim3((nn + 255) / 256), dim3(256), 0, c->stream, g->pos, g->scale, g->quat, c->upd_s, nn, c->upd_lo, c->upd_hi);
+            CHK(c, hipMemsetAsync(c->upd_in_tree, 0, n, c->stream));
+            CHK(c, hipMemsetAsync(c->upd_flag, 0, sizeof(uint32_t), c->stream));
+            if (m) hipLaunchKernelGGL(k_mark_in_tree, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->d_rec, m, nn, c->upd_in_tree);
+            hipLaunchKernelGGL(k_set_changed, dim3((nn + 255) / 256), dim3(256), 0, c->stream, c->upd_lo, c->upd_hi, c->upd_in_tree, nn, c->upd_flag);
+            CHK(c, hipMemcpyAsync(&h_flag, c->upd_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            CHK(c, hipStreamSynchronize(c->stream));
+            CHK(c, hipGetLastError());
+            if (h_flag) { reason = GRT_UPDATE_REASON_SET_CHANGED; try_refit = false; }
+        }
+    }
+    if (mode == GRT_UPDATE_REFIT && !try_refit) {
+        c->err = std::string("grt_update_gaussians_device: a refit is not possible: ") + update_reason_text(reason) + " (the scene is unchanged)";
+        return GRT_ERR_INVALID;
+    }
+    // ---- the attributes, into the library's own arrays (the backward pass reads them by original id) ----
+    c->scene_epoch++;
+    if (n != c->n) {
+        free_gaussians(c);
+        if (n) {
+            CHK(c, hipMalloc(&c->d_pos, n * 3 * sizeof(float)));
+            CHK(c, hipMalloc(&c->d_scale, n * 3 * sizeof(float)));
+            CHK(c, hipMalloc(&c->d_quat, n * 4 * sizeof(float)));
+            CHK(c, hipMalloc(&c->d_opacity, n * sizeof(float)));
+            CHK(c, hipMalloc(&c->d_sh, n * 48 * sizeof(float)));
+            CHK(c, hipMalloc(&c->d_color0, n * sizeof(float4)));
+        }
+    }
+    c->h_opacity.assign(c->upd_h_opacity.begin(), c->upd_h_opacity.begin() + (n ? n : 0));
+    float copy_ms = 0.0f;
+    if (n) {
+        CHK(c, hipMemcpyAsync(c->d_pos, g->pos, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d_scale, g->scale, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d_quat, g->quat, n * 4 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d_opacity, g->opacity, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        CHK(c, hipMemcpyAsync(c->d_sh, g->sh, n * 48 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_color0, dim3((nn + 255) / 256), dim3(256), 0, c->stream, c->d_sh, nn, c->d_color0);
+        CHK(c, hipGetLastError());
+    }
+    c->n = n;
+    c->have_timing = false;
+    c->erec_valid = false;
+    float area_ratio = 1.0f;
+    if (try_refit && n) {
+        // ---- refit: primitive boxes, binary nodes by level, pbox / wnodes / qnodes, records ----
+        const uint32_t m = c->gbvh.n_prims;
+        double area_now = 0.0;
+        if (m) {
+            int rc = update_scratch_m(c, m);
+            if (rc != GRT_OK) return rc;
+            if (!(c->area_build > 0.0) && (rc = lbvh_child_area(&c->gbvh, c->upd_part, &c->area_build, c->stream, &c->err)) != GRT_OK) return rc;
+            hipLaunchKernelGGL(k_refit_prim_boxes, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->d_rec, c->d_pos, c->d_scale, c->d_quat, c->upd_s,
+                               c->upd_lo, c->upd_hi, m, nn, c->upd_lb_lo, c->upd_lb_hi);
+            if ((rc = refit_sorted_lbvh(c->upd_lb_lo, c->upd_lb_hi, &c->gbvh, c->has_pieces, c->stream, &c->err)) != GRT_OK) return rc;
+            hipLaunchKernelGGL(k_regather_records, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->d_pos, c->d_scale, c->d_quat, c->d_opacity, c->upd_s,
+                               m, nn, c->d_rec);
+            CHK(c, hipEventRecord(c->ev_upd1, c->stream));
+            if ((rc = lbvh_child_area(&c->gbvh, c->upd_part, &area_now, c->stream, &c->err)) != GRT_OK) return rc;
+        } else {
+            CHK(c, hipEventRecord(c->ev_upd1, c->stream));
+        }
+        CHK(c, hipStreamSynchronize(c->stream));
+        CHK(c, hipGetLastError());
+        c->alpha_min = alpha_min;
+        c->n_hittable = n_hit;
+        if (c->area_build > 0.0 && area_now > 0.0) area_ratio = (float)(area_now / c->area_build);
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, c->ev_upd0, c->ev_upd1);
+        const bool guard = mode == GRT_UPDATE_AUTO && c->opt_refit_max_area_pct > 0 && !(area_ratio * 100.0f <= (float)c->opt_refit_max_area_pct);
+        if (!guard) {
+            if (out) { out->mode_used = GRT_UPDATE_REFIT; out->reason = GRT_UPDATE_REASON_NONE; out->device_ms = ms; out->area_ratio = area_ratio; }
+            return GRT_OK;
+        }
+        reason = GRT_UPDATE_REASON_AREA; // the boxes of this hierarchy no longer fit the scene: build a new one, in the same call
+        copy_ms = ms;
+    } else if (try_refit) { // n = 0 then and now: nothing to refit
+        if (out) { out->mode_used = GRT_UPDATE_REFIT; out->area_ratio = 1.0f; }
+        return GRT_OK;
+    } else if (n) {
+        CHK(c, hipEventRecord(c->ev_upd1, c->stream));
+        CHK(c, hipStreamSynchronize(c->stream));
+        (void)hipEventElapsedTime(&copy_ms, c->ev_upd0, c->ev_upd1);
+    }
+    // ---- rebuild: grt_build_bvh's own body, from the s computed above ----
+    const int rc = build_gaussian_bvh(c, alpha_min, c->upd_h_s.data());
+    if (rc != GRT_OK) return rc;
+    if (out) { out->mode_used = GRT_UPDATE_REBUILD; out->reason = reason; out->device_ms = copy_ms + (n ? c->build_ms : 0.0f); out->area_ratio = 1.0f; }
+    return GRT_OK;
 }
 
 int grt_set_meshes(grt_ctx* c, const grt_mesh* meshes, uint32_t n_meshes)
@@ -1124,6 +1414,9 @@ int grt_get_memory_info(const grt_ctx* c, grt_memory_info* o)
     if (sc->gbvh.wnodes && m > 1) b += (m - 1) * 128;                         // 4-wide view
     if (sc->gbvh.qnodes && m > 1) b += (m - 1) * 32ull * kTileWide;           // 8-wide per-child view
     if (sc->gbvh.pbox) b += m * 32;
+    if (sc->gbvh.level && m > 1) b += (m - 1) * 4;                            // levels, kept from the first refit on
+    b += sc->upd_cap_n * (4 + 16 + 16 + 1) + sc->upd_cap_m * 32;              // scratch of grt_update_gaussians_device ...
+    b += (sc->upd_flag ? 4 : 0) + (sc->upd_part ? kAreaParts * 8 : 0);
     b += nf * (48 + 12) + nv * 12 + sc->mbvh.cap_nodes * 64 + sc->mbvh.cap_order * 4 + (sc->mbvh.wnodes && nf > 1 ? (nf - 1) * 128 : 0) +
          (sc->mbvh.level && nf > 1 ? (nf - 1) * 4 : 0);
     o->scene_bytes = b;

@@ -1264,6 +1264,73 @@ fail:
     return GRT_ERR_HIP;
 }
 
+// ---- refit of the Gaussian tree (grt_update_gaussians_device) ----
+// Child half-areas of the binary records, per workgroup in a fixed order (lanes by shuffles, waves sequentially, the host adds the
+// partials): the same tree gives the same sum on every run.  Records below a collapsed leaf range are never reached by a traversal;
+// they are counted all the same — the build gave them boxes, a refit gives them boxes again, so the ratio of two sums compares like
+// with like.
+__global__ __launch_bounds__(256) void k_child_area_partial(const float4* __restrict__ nodes, int m, double* __restrict__ part)
+{
+    double sum = 0.0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m - 1; i += gridDim.x * blockDim.x) {
+        const float4 q0 = nodes[(size_t)i * 4], q1 = nodes[(size_t)i * 4 + 1], q2 = nodes[(size_t)i * 4 + 2];
+        const float b0[6] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y}, b1[6] = {q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+        sum += (double)box_area6(b0) + (double)box_area6(b1);
+    }
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    __shared__ double ssum[4];
+    if ((threadIdx.x & 63) == 0) ssum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((ssum[0] + ssum[1]) + ssum[2]) + ssum[3];
+}
+
+int lbvh_child_area(const DevBvh* bvh, double* d_part, double* out, hipStream_t stream, std::string* err)
+{
+    *out = 0.0;
+    const uint32_t m = bvh->n_prims;
+    if (m < 2 || (bvh->root_ref & kLeafBit) || !bvh->nodes) return GRT_OK;
+    const uint32_t grid = std::min<uint32_t>((m - 1 + 255u) / 256u, kAreaParts);
+    double h_part[kAreaParts];
+    hipLaunchKernelGGL(k_child_area_partial, dim3(grid), dim3(256), 0, stream, bvh->nodes, (int)m, d_part);
+    HIPCHK(hipMemcpyAsync(h_part, d_part, grid * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (uint32_t b = 0; b < grid; b++) *out += h_part[b];
+    return GRT_OK;
+fail:
+    return GRT_ERR_HIP;
+}
+
+int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh, bool widen_area_only, hipStream_t stream, std::string* err)
+{
+    const uint32_t m = bvh->n_prims;
+    const int B = 256;
+    const uint32_t grid = m > 1 ? (m - 1 + B - 1) / B : 1u;
+    if (m == 0) return GRT_OK;
+    if (bvh->pbox) hipLaunchKernelGGL(k_pbox, dim3((m + B - 1) / B), dim3(B), 0, stream, d_lb_lo, d_lb_hi, m, bvh->pbox);
+    if (bvh->root_ref & kLeafBit) { HIPCHK(hipGetLastError()); return GRT_OK; } // one leaf range: no node arrays
+    if (!bvh->nodes || !bvh->wnodes) {
+        if (err) *err = "refit_sorted_lbvh: the tree has no node arrays";
+        return GRT_ERR_INVALID;
+    }
+    if (!bvh->level) {
+        // The build did not keep its levels (a scene that is never updated pays no memory for them): number the topology as it stands,
+        // as the build does behind a rotation sweep.  A node's level is at most the height the build reported — the root's level over
+        // the uncollapsed tree, or over the rotated one — so `height` passes number every record, those below collapsed ranges included.
+        HIPCHK(hipMalloc(&bvh->level, sizeof(uint32_t) * (m - 1)));
+        HIPCHK(hipMemsetAsync(bvh->level, 0, sizeof(uint32_t) * (m - 1), stream));
+        for (uint32_t pass = 1; pass <= bvh->height; pass++)
+            hipLaunchKernelGGL(k_level_pass, dim3(grid), dim3(B), 0, stream, bvh->nodes, bvh->level, (int)m, pass);
+    }
+    for (uint32_t pass = 1; pass <= bvh->height; pass++)
+        hipLaunchKernelGGL(k_refit_level, dim3(grid), dim3(B), 0, stream, bvh->nodes, bvh->level, (int)m, pass, d_lb_lo, d_lb_hi);
+    hipLaunchKernelGGL(k_widen, dim3(grid), dim3(B), 0, stream, bvh->nodes, (int)m, bvh->wnodes);
+    if (bvh->qnodes) hipLaunchKernelGGL(k_qwiden, dim3(grid), dim3(B), 0, stream, bvh->nodes, (int)m, bvh->qnodes, widen_area_only ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return GRT_OK;
+fail:
+    return GRT_ERR_HIP;
+}
+
 int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t leaf_max, bool want_quad, bool keep_levels,
                int size_classes, DevBvh* out, hipStream_t stream, std::string* err, bool widen_area_only, int rotation_sweeps)
 {

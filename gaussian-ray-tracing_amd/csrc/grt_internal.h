@@ -61,6 +61,14 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
 // Re-fit every reachable node's boxes to new primitive boxes (same primitives, same order, same hierarchy): what a
 // gizmo drag needs (reference: full GAS + IAS rebuild per frame, src/GaussianTracer.cpp:711-794).
 int refit_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, DevBvh* bvh, hipStream_t stream, std::string* err);
+// The Gaussian tree re-fitted to new boxes of its primitives GIVEN IN SORTED ORDER (lb_lo / lb_hi [n_prims]: grt_api.hip k_refit_prim_boxes):
+// pbox, the binary nodes level by level (bvh->level is derived from the topology when the build did not keep it, and stays), wnodes, qnodes.
+// Queues its work on the stream and does not wait for it.
+int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh, bool widen_area_only, hipStream_t stream, std::string* err);
+// sum over the binary node records of the half-areas of the two child boxes they hold (0 for a tree without internal nodes): per-workgroup
+// partials in d_part (kAreaParts doubles) in a fixed order, added on the host; synchronises the stream
+constexpr uint32_t kAreaParts = 256u;
+int lbvh_child_area(const DevBvh* bvh, double* d_part, double* out, hipStream_t stream, std::string* err);
 void free_bvh(DevBvh* b);
 // exclusive scan of n uint32 values on the device (hand-written, grt_bvh.hip); synchronises the stream
 int device_exclusive_scan_u32(const uint32_t* d_in, uint32_t* d_out, uint32_t n, hipStream_t stream, std::string* err);
@@ -422,4 +430,18 @@ struct grt_ctx {
     bool bwd_pending = false;
     hipStream_t bwd_stream = nullptr;
     int opt_bwd_plain = 0;                  // GRT_OPT_BWD_PLAIN_ATOMICS
+    // device-resident scene update (grt_api.hip: grt_update_gaussians_device)
+    int opt_refit_max_area_pct = 200;       // GRT_OPT_REFIT_MAX_AREA_PCT
+    int built_opts[5] = {0, 0, 0, 0, 0};    // GRT_OPT_LEAF_MAX, _SIZE_CLASSES, _SPLIT, _SPLIT_VOL_PCT, _BVH_ROTATIONS of the last build
+    double area_build = 0.0;                // child half-areas of the tree as BUILT (0 = not measured yet: the first refit measures it)
+    // ... its scratch, made by the first update and kept: s, the proxy boxes by particle [upd_cap_n]; the primitive boxes in sorted
+    // order [upd_cap_m]; one byte per particle "is in the tree"; the word that says the set changed; the partial sums of the area
+    float* upd_s = nullptr;
+    float4 *upd_lo = nullptr, *upd_hi = nullptr, *upd_lb_lo = nullptr, *upd_lb_hi = nullptr;
+    uint8_t* upd_in_tree = nullptr;
+    uint32_t* upd_flag = nullptr;
+    double* upd_part = nullptr;
+    uint64_t upd_cap_n = 0, upd_cap_m = 0;
+    std::vector<float> upd_h_opacity, upd_h_s;
+    hipEvent_t ev_upd0 = nullptr, ev_upd1 = nullptr;
 };

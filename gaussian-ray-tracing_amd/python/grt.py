@@ -66,6 +66,15 @@ class GaussianGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "sh")]
 
 
+class UpdateInfo(C.Structure):
+    """grt_update_info (include/grt.h): what grt_update_gaussians_device did."""
+    _fields_ = [("mode_used", C.c_uint32), ("reason", C.c_uint32), ("device_ms", C.c_float), ("area_ratio", C.c_float)]
+
+
+UPDATE_AUTO, UPDATE_REFIT, UPDATE_REBUILD = 0, 1, 2
+UPDATE_MODES = {"auto": UPDATE_AUTO, "refit": UPDATE_REFIT, "rebuild": UPDATE_REBUILD}
+REASON_NONE, REASON_FIRST_BUILD, REASON_N_CHANGED, REASON_SET_CHANGED, REASON_OPTION_CHANGED, REASON_AREA = 0, 1, 2, 3, 4, 5
+
 GRAD_SHAPES = {"pos": (3,), "scale": (3,), "quat": (4,), "opacity": (), "sh": (16, 3)}
 
 
@@ -91,11 +100,13 @@ OPT_BUNDLE_PREDICT = 36
 OPT_MESH_PRIMARY_WAVE = 37
 OPT_SPLIT_VOL_PCT = 38
 OPT_BWD_PLAIN_ATOMICS = 39
+OPT_REFIT_MAX_AREA_PCT = 40
 ERR_LIMIT = -5
 KERNEL_AUTO, KERNEL_PERLANE, KERNEL_WAVE, KERNEL_STREAM, KERNEL_STREAM_BIG, KERNEL_TILE = 0, 1, 2, 3, 4, 5
 
 EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
+    "grt_update_gaussians_device",
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
@@ -132,6 +143,7 @@ def lib():
         L.grt_set_option.argtypes = [vp, C.c_int, C.c_int]
         L.grt_upload_gaussians.argtypes = [vp, C.POINTER(Gaussians), u64]
         L.grt_build_bvh.argtypes = [vp, fl]
+        L.grt_update_gaussians_device.argtypes = [vp, C.POINTER(Gaussians), u64, fl, C.c_int, vp, C.POINTER(UpdateInfo)]
         L.grt_set_meshes.argtypes = [vp, C.POINTER(Mesh), u32]
         L.grt_update_meshes.argtypes = [vp, C.POINTER(Mesh), u32]
         L.grt_get_bvh_info.argtypes = [vp, C.POINTER(BvhInfo)]
@@ -363,6 +375,32 @@ class Tracer:
         g = Gaussians(*(a[k].ctypes.data for k in ("pos", "scale", "quat", "opacity", "sh")))
         self._check(lib().grt_upload_gaussians(self._h, C.byref(g), len(a["pos"])))
         self._check(lib().grt_build_bvh(self._h, alpha_min))
+
+    def update_device(self, acts, alpha_min=0.01, mode="auto"):
+        """grt_update_gaussians_device: the scene from a dict of CUDA tensors (pos [n][3], scale [n][3], quat [n][4], opacity [n],
+        sh [n][16][3]; made float32 and contiguous on the tracer's GPU when they are not), never through the host.  mode "auto" refits
+        the BVH in hand when that is possible and rebuilds it otherwise, "refit" raises when it is not, "rebuild" is upload() from
+        device memory.  Returns {'mode_used', 'reason', 'device_ms', 'area_ratio'} (include/grt.h: grt_update_info)."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        a = {k: t.as_tensor(acts[k]).detach().to(dev, t.float32).contiguous() for k in ("pos", "scale", "quat", "opacity", "sh")}
+        n = int(a["pos"].shape[0])
+        shapes = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,), "sh": (n, 16, 3)}
+        for k, v in a.items():
+            if tuple(v.shape) != shapes[k]:
+                raise GrtError(f"update_device: '{k}' has shape {tuple(v.shape)}, expected {shapes[k]}")
+        return self.update_device_ptrs(Gaussians(*(a[k].data_ptr() if n else None for k in ("pos", "scale", "quat", "opacity", "sh"))),
+                                       n, alpha_min, mode)
+
+    def update_device_ptrs(self, g, n, alpha_min=0.01, mode="auto"):
+        """(testing) update_device from a Gaussians struct of raw pointers, as the C ABI takes them."""
+        info = UpdateInfo()
+        rc = lib().grt_update_gaussians_device(self._h, C.byref(g), n, alpha_min, UPDATE_MODES.get(mode, mode), self._stream(), C.byref(info))
+        if rc == 0:  # (a refused update leaves the scene, and these, as they were)
+            self.n_particles = n
+            self.n_uploads += 1
+        self._check(rc)
+        return {n_: (int(getattr(info, n_)) if n_ in ("mode_used", "reason") else float(getattr(info, n_))) for n_, _ in info._fields_}
 
     def set_meshes(self, meshes):
         keep, arr = [], (Mesh * max(len(meshes), 1))()

@@ -4,8 +4,11 @@
     rgb, alpha = grt_torch.render(tracer, params, pos, scale, quat, opacity, sh, rays)    # ray buffer:   [n][3],    [n]
 
 The five tensors are the ACTIVATED attributes of grt_gaussians ([n][3] [n][3] [n][4] [n] [n][16][3]); the chain through exp /
-sigmoid / normalise is torch's, in the caller's own graph.  Every forward uploads them from host arrays and rebuilds the BVH (a
-device-resident upload is not part of this wrapper); Gaussian-only frames (a tracer with meshes set is refused by the backward).
+sigmoid / normalise is torch's, in the caller's own graph.  Leaves that all live on the tracer's GPU never touch the host: every
+forward hands them to Tracer.update_device, which refits the BVH in hand while the particles move a little and rebuilds it otherwise
+(update="auto"; "refit" / "rebuild" force one), and their gradients stay on the device.  CPU leaves are uploaded from
+host arrays with a rebuild, as before; mixed leaves are moved to the device.  `tracer.last_update` holds what the last device update
+did.  Gaussian-only frames (a tracer with meshes set is refused by the backward).
 The backward differentiates the scene the tracer HOLDS: it must run before the next upload to the same tracer (another
 grt_torch.render included), and raises GrtError otherwise.  Gradients with respect to rays / camera are not computed.  This is the only module of the package that imports torch at load.
 """
@@ -17,10 +20,13 @@ import grt
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos, scale, quat, opacity, sh, tracer, params, rays):
-        acts = {k: np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
-                for k, v in (("pos", pos), ("scale", scale), ("quat", quat), ("opacity", opacity), ("sh", sh))}
-        tracer.upload(acts, params.alpha_min)
+    def forward(ctx, pos, scale, quat, opacity, sh, tracer, params, rays, update):
+        leaves = (("pos", pos), ("scale", scale), ("quat", quat), ("opacity", opacity), ("sh", sh))
+        if any(v.is_cuda for _, v in leaves):
+            tracer.last_update = tracer.update_device({k: v for k, v in leaves}, params.alpha_min, update)
+        else:
+            acts = {k: np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for k, v in leaves}
+            tracer.upload(acts, params.alpha_min)
         ctx.upload_id = tracer.n_uploads
         if rays is None:
             out = tracer.render_aux(params, want_u8=False, want_f32=True, alpha=True, depth=False, count=False)
@@ -42,7 +48,7 @@ class _Render(torch.autograd.Function):
         names = ("pos", "scale", "quat", "opacity", "sh")
         groups = [n for n, want in zip(names, need) if want]
         if not groups:
-            return (None,) * 8
+            return (None,) * 9
         g_rgb = g_rgb.to(rgb.device, torch.float32).contiguous()
         g_alpha = g_alpha.to(rgb.device, torch.float32).contiguous() if g_alpha is not None else None
         if ctx.rays is None:
@@ -50,9 +56,12 @@ class _Render(torch.autograd.Function):
         else:
             g = tr.backward_rays(ctx.params, ctx.rays, rgb, alpha, g_rgb, g_alpha, groups=groups)
         out = tuple(g[n].to(dev, dt) if n in g else None for n, (dev, dt) in zip(names, ctx.like))
-        return out + (None, None, None)
+        return out + (None, None, None, None)
 
 
-def render(tracer, params, pos, scale, quat, opacity, sh, rays=None):
-    """(rgb, alpha) of the Gaussians given as torch tensors, differentiable with respect to all five (module docstring)."""
-    return _Render.apply(pos, scale, quat, opacity, sh, tracer, params, rays)
+def render(tracer, params, pos, scale, quat, opacity, sh, rays=None, update="auto"):
+    """(rgb, alpha) of the Gaussians given as torch tensors, differentiable with respect to all five (module docstring).
+    update: what a forward with CUDA leaves asks of Tracer.update_device — "auto", "refit" or "rebuild"."""
+    if update not in grt.UPDATE_MODES:
+        raise ValueError(f"grt_torch.render: update must be one of {sorted(grt.UPDATE_MODES)}, not {update!r}")
+    return _Render.apply(pos, scale, quat, opacity, sh, tracer, params, rays, update)

@@ -15,6 +15,8 @@
  *   grt_upload_gaussians          particle upload in initializeParams      src/GaussianTracer.cpp:491-502
  *   grt_build_bvh                 createGaussianParticlesBVH/createGAS/    src/GaussianTracer.cpp:297-317,
  *                                 buildAccelationStructure (OptiX, closed)   319-399, 422-473
+ *   grt_update_gaussians_device   (new) the scene of an optimisation step: attributes from DEVICE memory, the LBVH re-fitted
+ *                                 instead of rebuilt while the particles move a little
  *   grt_set_meshes                createGAS+createIAS for primitives,      src/GaussianTracer.cpp:578-709
  *                                 sendGeometryAttributesToDevice
  *   grt_update_meshes             updateInstanceTransforms (refit, no rebuild) src/GaussianTracer.cpp:711-794
@@ -245,13 +247,16 @@ enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_count
                                            next build.  Same pixels */,
        GRT_OPT_BWD_PLAIN_ATOMICS = 39   /* (testing) backward pass: 1 = every lane adds its own 14 values per event to its particle's row of the
                                            gradient buffer; 0 (default): lanes of a wave that composite the same particle in the same slot
-                                           of their k-buffers reduce over the wave first.  Same gradients within the float32 tolerance */ };
+                                           of their k-buffers reduce over the wave first.  Same gradients within the float32 tolerance */,
+       GRT_OPT_REFIT_MAX_AREA_PCT = 40  /* grt_update_gaussians_device with GRT_UPDATE_AUTO: a refit that leaves grt_update_info::area_ratio above
+                                           value / 100 is followed by a rebuild in the same call (default 200: DESIGN.md 5.9; 0 = never).  A forced
+                                           GRT_UPDATE_REFIT never rebuilds.  Refused on a view.  Culling structure only: same pixels */ };
 
 /* ---- context ---- */
 GRT_API int grt_create(grt_ctx** out, int device);
 /* A view: a frame slot of its own (stream, eye records, scheduling feedback, overflow pool, queues, counters, error
  * word) that renders `scene`'s Gaussians, BVHs and meshes.  Scene calls (grt_upload_gaussians, grt_build_bvh,
- * grt_set_meshes, grt_update_meshes, GRT_OPT_LEAF_MAX / GRT_OPT_SIZE_CLASSES) are refused on a view.  Destroying a
+ * grt_update_gaussians_device, grt_set_meshes, grt_update_meshes, GRT_OPT_LEAF_MAX / GRT_OPT_SIZE_CLASSES) are refused on a view.  Destroying a
  * scene with live views is deferred until the last view is destroyed. */
 GRT_API int grt_create_view(grt_ctx* scene, grt_ctx** out);
 GRT_API void grt_destroy(grt_ctx* ctx);
@@ -261,6 +266,42 @@ GRT_API int grt_set_option(grt_ctx* ctx, int option, int value);
 /* ---- scene ---- */
 GRT_API int grt_upload_gaussians(grt_ctx* ctx, const grt_gaussians* host, uint64_t n);
 GRT_API int grt_build_bvh(grt_ctx* ctx, float alpha_min);
+/* The scene of a training step: the five attribute arrays from DEVICE memory (the layout and meaning of grt_gaussians: activated
+ * values, quat normalised; contiguous float32), and the Gaussian BVH brought up to date.  The call synchronises the device, so its
+ * reads are ordered after everything queued before it — on `stream` (a hipStream_t, NULL = the context's own; the convention of
+ * grt_render's stream argument) as on any other — and the caller may overwrite its arrays as soon as it returns: the library keeps
+ * copies of its own (the backward pass reads them by original id).  n has the limit of grt_upload_gaussians.  A pointer that is not
+ * device memory of the context's GPU, a NULL pointer with n > 0, and a view are refused with GRT_ERR_INVALID.
+ *   GRT_UPDATE_REBUILD  grt_upload_gaussians + grt_build_bvh from device memory: the same tree, array for array (the build is
+ *                       deterministic).
+ *   GRT_UPDATE_REFIT    keeps the sorted order, the hierarchy and the leaf ranges of the tree in hand and recomputes, in this
+ *                       sequence: the primitive boxes; the binary nodes' boxes, level by level (the levels are derived on the
+ *                       first refit of a tree); the per-primitive boxes, the 4-wide and per-child views and the proxy records.
+ *                       A piece of a split proxy keeps its particle and its cell (any grid partitions the proxy-local box: a
+ *                       stale piece length costs speed, never hits); the cell's box follows the particle's new values.
+ *                       Possible when a tree is built, n is unchanged, the build options (GRT_OPT_LEAF_MAX, _SIZE_CLASSES,
+ *                       _SPLIT, _SPLIT_VOL_PCT, _BVH_ROTATIONS) are those of the last build, and the set of particles in the
+ *                       tree — hittable (opacity > alpha_min) and finite — is unchanged (decided on the device).  Otherwise:
+ *                       GRT_ERR_INVALID, the reason in grt_last_error, the scene left as it was before the call.
+ *   GRT_UPDATE_AUTO     refits when possible, rebuilds otherwise — and rebuilds behind a refit that left area_ratio above
+ *                       GRT_OPT_REFIT_MAX_AREA_PCT (an unrelated scene that happens to have the same n).
+ * The proxy half-width s = sqrtf(2 logf(opacity / alpha_min)) stays the HOST libm's, as in grt_build_bvh: the opacities are read
+ * back (4 B per particle), s is computed on at most 16 threads and sent up.  An update with the n of the last one allocates and
+ * frees no scene memory on the refit path.  Pixels never depend on the mode: the tree only culls. */
+enum { GRT_UPDATE_AUTO = 0, GRT_UPDATE_REFIT = 1, GRT_UPDATE_REBUILD = 2 };
+enum { GRT_UPDATE_REASON_NONE = 0, GRT_UPDATE_REASON_FIRST_BUILD = 1, GRT_UPDATE_REASON_N_CHANGED = 2,
+       GRT_UPDATE_REASON_SET_CHANGED = 3 /* the hittable, finite particles are not those in the tree */,
+       GRT_UPDATE_REASON_OPTION_CHANGED = 4, GRT_UPDATE_REASON_AREA = 5 };
+typedef struct {
+    uint32_t mode_used;   /* GRT_UPDATE_REFIT or GRT_UPDATE_REBUILD: what was done */
+    uint32_t reason;      /* GRT_UPDATE_REASON_*: why GRT_UPDATE_AUTO rebuilt (0 after a refit and after a rebuild that was asked for) */
+    float    device_ms;   /* device time of the update on the context's stream, from behind the upload of s to its last kernel (the
+                             one-word readback of the set test included; a rebuild: the copies + grt_bvh_info::build_ms) */
+    float    area_ratio;  /* sum over the binary nodes of their two child boxes' half-areas, now / at the last BUILD (1.0 after a
+                             build and for a tree without internal nodes) */
+} grt_update_info;
+GRT_API int grt_update_gaussians_device(grt_ctx* ctx, const grt_gaussians* dev, uint64_t n, float alpha_min, int mode,
+                                        void* stream, grt_update_info* out);
 GRT_API int grt_set_meshes(grt_ctx* ctx, const grt_mesh* meshes, uint32_t n_meshes);
 /* The same meshes, moved: new positions / normals for the topology of the last grt_set_meshes (same nv, nf per
  * mesh).  The mesh LBVH keeps its hierarchy and re-fits its boxes (reference: updateInstanceTransforms rebuilds GAS +
