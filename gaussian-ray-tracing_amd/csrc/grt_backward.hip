@@ -1,8 +1,8 @@
 // grt_backward.hip — the backward pass of Gaussian-only frames (include/grt.h: grt_backward / grt_backward_rays):
 // gradients of a loss on (rgbf, alpha) with respect to the activated attributes of the Gaussians, discrete decisions held fixed.
 //
-// A translation unit of its own (kernels AND entry points): no existing kernel's text moves.  One ray per lane, an 8x8 tile per
-// wave, k = 7 rounds on the per-lane traversal, exactly the walk of trace_gaussians (grt_render.hip), twice per ray:
+// A translation unit of its own (kernels AND entry points).  One ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round
+// (grt_kround.h: the round trace_gaussians of grt_render.hip runs, without its watchdog and counters), twice per ray:
 //   sweep 0  re-derives rad and T_end (the forward's own arithmetic, so the same events in the same order);
 //   sweep 1  walks the same events again and forms every composited event's terms with S_i = rad - C_<=i.
 // (d_rgbf / d_alpha are not read: rad = rgbf / A and T_end = 1 - alpha lose what the float32 subtraction 1 - T lost — an absolute
@@ -20,12 +20,14 @@
 
 #include "grt_device.h"
 #include "grt_internal.h"
+#include "grt_kround.h"
 
 namespace grt {
 namespace {
 
 constexpr int K = 7;       // MaxNumHitPerTrace, shaders/tracer.cuh:11
 constexpr int kBlock = 256;
+static_assert(kBlock == kRoundBlock, "the per-lane stack stride of gps_round (grt_kround.h) is the launch block size");
 constexpr int kRow = 16;   // floats per particle row of the gradient buffer
 constexpr int kShHi = 45;  // floats per particle of the higher-SH buffer
 constexpr int kVals = 14;  // pos 3, scale 3, quat 4, opacity 1, sh0 3
@@ -42,110 +44,6 @@ struct BwdArgs {
     uint32_t want_geom;    // pos / scale / quat / opacity asked for (else their terms are not formed)
     uint32_t want_sh;
 };
-
-struct KBuf {
-    uint64_t key[K];
-    float alpha[K];
-};
-
-__device__ __forceinline__ void kbuf_insert(KBuf& kb, uint64_t key, float alpha)
-{
-    if (key >= kb.key[K - 1]) return;
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        if (key == kb.key[i]) return; // the same event again: a split particle met through another of its pieces
-        if (key < kb.key[i]) {
-            const uint64_t tk = kb.key[i];
-            const float ta = kb.alpha[i];
-            kb.key[i] = key;
-            kb.alpha[i] = alpha;
-            key = tk;
-            alpha = ta;
-        }
-    }
-}
-
-// one k-nearest round: gps_round of grt_render.hip (same tests in the same order: the same k-buffer)
-__device__ __forceinline__ void bwd_round(const RenderArgs& a, uint32_t* __restrict__ stk, f3 o, f3 d, const rayinv& ri,
-                                       uint64_t last_key, float t_hi, KBuf& kb)
-{
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        kb.key[i] = kKeyInvalid;
-        kb.alpha[i] = 0.0f;
-    }
-    const float t_lo = key_t(last_key);
-    float bound = t_hi;
-    uint32_t sp = 0;
-    uint32_t cur = a.root_ref;
-    while (true) {
-        if (cur & kLeafBit) {
-            const uint32_t first = leaf_first(cur), cnt = leaf_count(cur);
-            for (uint32_t j = 0; j < cnt; j++) {
-                const float4* __restrict__ r = a.rec + (size_t)(first + j) * 4;
-                const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-                const f3 mu = mk3(r0.x, r0.y, r0.z);
-                m33 A;
-                A.a[0] = r1.x; A.a[1] = r1.y; A.a[2] = r1.z;
-                A.a[3] = r2.x; A.a[4] = r2.y; A.a[5] = r2.z;
-                A.a[6] = r3.x; A.a[7] = r3.y; A.a[8] = r3.z;
-                const f3 o_g = matvec(A, sub3(o, mu));
-                const f3 d_g = matvec(A, d);
-                float te, tx;
-                if (proxy_sphere_maybe(o_g, d_g, r0.w) && proxy_slabs(o_g, d_g, r0.w, te, tx)) {
-                    const uint32_t cellb = __float_as_uint(r3.w);
-                    const bool in_e = (te >= t_lo) && (te < t_hi) && (!cellb || piece_owns(cellb, r0.w, o_g, d_g, te));
-                    const bool in_x = (tx >= t_lo) && (tx < t_hi) && (!cellb || piece_owns(cellb, r0.w, o_g, d_g, tx));
-                    if (in_e || in_x) {
-                        const float alpha = fminf(0.99f, response_from(A, mu, o, d, o_g, d_g) * r1.w);
-                        const uint32_t id = __float_as_uint(r2.w);
-                        if (in_e) {
-                            const uint64_t k = mk_key(te, id, 0);
-                            if (k > last_key) kbuf_insert(kb, k, alpha);
-                        }
-                        if (in_x) {
-                            const uint64_t k = mk_key(tx, id, 1);
-                            if (k > last_key) kbuf_insert(kb, k, alpha);
-                        }
-                        if (kb.key[K - 1] != kKeyInvalid) bound = key_t(kb.key[K - 1]);
-                    }
-                }
-            }
-            if (sp == 0) break;
-            cur = stk[(--sp) * kBlock];
-        } else {
-            const float4* __restrict__ q = a.nodes + (size_t)cur * 4;
-            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-            float n0, f0, n1, f1;
-            box_interval(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, ri, n0, f0);
-            box_interval(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, ri, n1, f1);
-            const bool h0 = (n0 <= f0) && (f0 >= t_lo) && (n0 <= bound);
-            const bool h1 = (n1 <= f1) && (f1 >= t_lo) && (n1 <= bound);
-            const uint32_t c0 = __float_as_uint(q3.x), c1 = __float_as_uint(q3.y);
-            if (h0 && h1) {
-                const bool first0 = n0 <= n1;
-                stk[(sp++) * kBlock] = first0 ? c1 : c0;
-                cur = first0 ? c0 : c1;
-            } else if (h0) {
-                cur = c0;
-            } else if (h1) {
-                cur = c1;
-            } else {
-                if (sp == 0) break;
-                cur = stk[(--sp) * kBlock];
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ f3 event_radiance(const RenderArgs& a, uint32_t id, f3 dn)
-{
-    if (a.p.sh_degree_max == 0) {
-        const float4 cc = a.color0[id];
-        return mk3(cc.x, cc.y, cc.z);
-    }
-    return sh_radiance(a.sh + (size_t)id * 48, dn, a.p.sh_degree_max);
-}
 
 // the basis of sh_radiance (grt_device.h): L = max(0, 0.5 + sum_k Y[k] sh_k); Y[1 .. (deg + 1)^2 - 1] are filled (deg >= 1)
 __device__ __forceinline__ void sh_basis(f3 d, uint32_t deg, float Y[16])
@@ -358,7 +256,8 @@ __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const B
     const float t_hi = t_max + epsT;
     const float minT = a.p.minTransmittance;
     const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
-    KBuf kb;
+    KBuf<K> kb;
+    Cnt cnt; // (dead: no counters, no watchdog)
 
     // ---- two sweeps over the same events through ONE call site of the traversal (every lane of the wave in step: the scatter of
     //      sweep 1 is wave-cooperative).  Sweep 0: rad and T_end, trace() as the forward runs it (shaders/tracer.cuh:328-373);
@@ -373,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const B
         bool act = live && (lastT <= t_max) && (T > minT);
         while (__builtin_amdgcn_ballot_w64(act)) {
             if (act) {
-                bwd_round(a, stk, o, d, ri, last_key, t_hi, kb);
+                gps_round<false, false, K>(a, stk, o, d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
                 if (kb.key[0] == kKeyInvalid) act = false;
             }
 #pragma unroll 1
