@@ -552,7 +552,10 @@ def check_gaussian_tree(dump, particles, alpha_min=0.01, n_primitives=None, g5_p
             okc = (pl <= clo).all(1) & (ph >= chi).all(1)
             F.check("G4", okc, lambda i: f"piece {jp[i]} (particle {ids_c[jp[i]]}, cell {k[i].tolist()} of {p[i].tolist()}): box "
                                          f"{lo[jp[i]].tolist()} .. {hi[jp[i]].tolist()} misses a corner of its cell {clo[i].tolist()} .. {chi[i].tolist()}")
-            inside = (pl >= vw.min(1) - 1e-5 * (1 + np.abs(vw.min(1))) * 4).all(1) & (ph <= vw.max(1) + 1e-5 * (1 + np.abs(vw.max(1))) * 4).all(1)
+            # (the builder widens a proxy's box on BOTH sides of an axis by 1e-5 (1 + the larger |coordinate| of that axis): a long proxy far
+            #  from the origin, -98 .. -20 say, gets at -20 the margin of -98.  Four times that margin, on either side.)
+            tol = 4e-5 * (1 + np.maximum(np.abs(vw.min(1)), np.abs(vw.max(1))))
+            inside = (pl >= vw.min(1) - tol).all(1) & (ph <= vw.max(1) + tol).all(1)
             F.check("G4", inside, lambda i: f"piece {jp[i]} (particle {ids_c[jp[i]]}): box reaches outside the whole proxy's box")
             F.check("G4", np.isposinf(rad[jp]), lambda i: f"piece {jp[i]}: radius {rad[jp[i]]!r}, a piece has none (+inf)")
     # ---- G2 + G3 ----

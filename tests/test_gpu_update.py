@@ -163,14 +163,15 @@ def start_of(acts):
     return d, float((d["pos"] - c).norm(dim=1).max())
 
 
-def check_step(tr, d, p, what, **kw):
-    """the refitted tree against the new values in float64, and its frames against a fresh tracer's after a host upload"""
+def check_step(tr, d, p, what, kernels=(0, 1), options=(), **kw):
+    """the refitted tree against the new values in float64, and its frames against a fresh tracer's after a host upload (built with
+    `options`, the build options of `tr`)"""
     h = host(d)
     info = tr.bvh_info()
     rep = check_gaussian_tree(tr.debug_tree(0), h, 0.01, n_primitives=info["n_primitives"], **kw)
-    fresh = host_tracer(h)
+    fresh = host_tracer(h, options)
     try:
-        for kernel in (0, 1):
+        for kernel in kernels:
             assert_same_frame(frame(tr, p, kernel), frame(fresh, p, kernel), f"{what} kernel {kernel}")
     finally:
         fresh.close()
