@@ -12,6 +12,11 @@
 // streaming kernel that also zeroes the buffer.  MERGE: the lanes of the wave that composite the same particle in the same slot
 // of their k-buffers reduce their 14 values over the wave first (DPP inside rows of 16, v_readlane across) and 14 lanes add one
 // float each to the particle's contiguous row; a lane alone with its particle adds its own.  Only vector atomics write memory.
+//
+// grt_backward_rays.hip includes this file with GRT_BWD_RAYS_TU defined (the technique of grt_render_tile_aux.hip): the same two
+// sweeps, event_terms and scatter, the kernel named k_backward_rays<MERGE, GAUSS> with the per-ray output as a third argument, and
+// none of this unit's flush kernels and entry points.  Without the macro every addition below is compiled away: this unit's
+// assembly is what it was before them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,6 +49,44 @@ struct BwdArgs {
     uint32_t want_geom;    // pos / scale / quat / opacity asked for (else their terms are not formed)
     uint32_t want_sh;
 };
+
+// What one ray collects for grt_backward_ex (GRT_BWD_RAYS_TU): -dloss/do, the geometry part of dloss/dd, and g_dn (include/grt.h)
+struct RayAcc {
+    f3 go, gd, gdn;
+};
+#ifdef GRT_BWD_RAYS_TU
+struct RayOut {
+    float* rays;           // [pixels or rays][6], written
+    uint32_t scatter_geom; // the caller asked for pos / scale / quat / opacity (b.want_geom is set for the rays' sake as well)
+};
+// sum_k (dY_k/dn)(dn) c_k with c_k = sh_k . gL: the polynomials of sh_basis differentiated in x, y, z (deg >= 1)
+__device__ __forceinline__ f3 sh_basis_grad(const float* __restrict__ sh, f3 gL, f3 d, uint32_t deg)
+{
+#define GRT_SHC(i) (sh[(i) * 3] * gL.x + sh[(i) * 3 + 1] * gL.y + sh[(i) * 3 + 2] * gL.z)
+    const float x = d.x, y = d.y, z = d.z;
+    f3 g = mk3(-GRT_SH_C1 * GRT_SHC(3), -GRT_SH_C1 * GRT_SHC(1), GRT_SH_C1 * GRT_SHC(2));
+    if (deg < 2u) return g;
+    {
+        const float c4 = GRT_SH_C2_0 * GRT_SHC(4), c5 = GRT_SH_C2_1 * GRT_SHC(5), c6 = GRT_SH_C2_2 * GRT_SHC(6);
+        const float c7 = GRT_SH_C2_3 * GRT_SHC(7), c8 = GRT_SH_C2_4 * GRT_SHC(8);
+        g.x += ((c4 * y + c7 * z) + 2.0f * (c8 - c6) * x);
+        g.y += ((c4 * x + c5 * z) - 2.0f * (c8 + c6) * y);
+        g.z += ((c5 * y + c7 * x) + 4.0f * c6 * z);
+    }
+    if (deg < 3u) return g;
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
+    const float c9 = GRT_SH_C3_0 * GRT_SHC(9), c10 = GRT_SH_C3_1 * GRT_SHC(10), c11 = GRT_SH_C3_2 * GRT_SHC(11);
+    const float c12 = GRT_SH_C3_3 * GRT_SHC(12), c13 = GRT_SH_C3_4 * GRT_SHC(13), c14 = GRT_SH_C3_5 * GRT_SHC(14);
+    const float c15 = GRT_SH_C3_6 * GRT_SHC(15);
+    g.x += (((6.0f * c9 - 2.0f * c11) * xy + c10 * yz) + ((2.0f * c14 - 6.0f * c12) * xz + c13 * (4.0f * zz - 3.0f * xx - yy))) +
+           3.0f * c15 * (xx - yy);
+    g.y += (((3.0f * c9) * (xx - yy) + c10 * xz) + (c11 * (4.0f * zz - xx - 3.0f * yy) - (6.0f * c12 + 2.0f * c14) * yz)) -
+           (2.0f * c13 + 6.0f * c15) * xy;
+    g.z += ((c10 * xy + 8.0f * (c11 * yz + c13 * xz)) + (3.0f * c12) * (2.0f * zz - xx - yy)) + c14 * (xx - yy);
+#undef GRT_SHC
+    return g;
+}
+#endif
 
 // the basis of sh_radiance (grt_device.h): L = max(0, 0.5 + sum_k Y[k] sh_k); Y[1 .. (deg + 1)^2 - 1] are filled (deg >= 1)
 __device__ __forceinline__ void sh_basis(f3 d, uint32_t deg, float Y[16])
@@ -126,8 +169,11 @@ __device__ __forceinline__ void scatter(float* __restrict__ acc, bool ev, uint32
 // The terms of one composited event (sweep 1): v[0..13] = what it adds to pos 3, scale 3, quat 4, opacity, sh_0 3 of particle id (the
 // higher SH coefficients go to their buffer from here: one lane, one direction — nothing to merge across the wave).  T: the
 // transmittance before the event; S: what lies behind it (rad - C_<=i).  Returns whether the geometry / opacity terms were formed.
+// GAUSS: the Gaussians' gradients are wanted at all (else no atomic is in the text); RAYS: the event's part of the ray's gradient
+// goes to ra — m = A^T g_p (v[0..2]) to the origin, d_val m to the direction, the colour's direction derivative to g_dn.
+template <bool GAUSS, bool RAYS>
 __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& b, uint32_t id, f3 o, f3 d, f3 dn, f3 L, float T, float hitAlpha,
-                                            f3 S, f3 g_rad, float gAp, float Tend, float v[kVals])
+                                            f3 S, f3 g_rad, float gAp, float Tend, float v[kVals], RayAcc& ra)
 {
     bool geom = false;
     const float w = T * hitAlpha;
@@ -136,7 +182,7 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
                        gAp * Tend * inv1;
     // colour: dloss/dL_c = T alpha g_rad_c where L_c > 0
     const f3 gL = mk3(L.x > 0.0f ? w * g_rad.x : 0.0f, L.y > 0.0f ? w * g_rad.y : 0.0f, L.z > 0.0f ? w * g_rad.z : 0.0f);
-    if (b.want_sh) {
+    if (GAUSS && b.want_sh) {
         v[11] = GRT_SH_C0 * gL.x; v[12] = GRT_SH_C0 * gL.y; v[13] = GRT_SH_C0 * gL.z;
         if (a.p.sh_degree_max > 0u) { // the higher coefficients: one lane, one direction — no merge across the wave
             float Y[16];
@@ -153,6 +199,9 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
             }
         }
     }
+#ifdef GRT_BWD_RAYS_TU
+    if (RAYS && a.p.sh_degree_max > 0u) ra.gdn = add3(ra.gdn, sh_basis_grad(a.sh + (size_t)id * 48, gL, dn, a.p.sh_degree_max));
+#endif
     if (b.want_geom && hitAlpha < 0.99f) { // (where the 0.99 clamp binds nothing goes into opacity or geometry)
         geom = true;
         const f3 mu = mk3(b.pos[id * 3], b.pos[id * 3 + 1], b.pos[id * 3 + 2]);
@@ -181,6 +230,10 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
         v[0] = A.a[0] * gp.x + A.a[3] * gp.y + A.a[6] * gp.z;
         v[1] = A.a[1] * gp.x + A.a[4] * gp.y + A.a[7] * gp.z;
         v[2] = A.a[2] * gp.x + A.a[5] * gp.y + A.a[8] * gp.z;
+        if (RAYS) { // d p_g / d o = -A, d p_g / d d = -d_val A (at fixed d_val)
+            ra.go = add3(ra.go, mk3(v[0], v[1], v[2]));
+            ra.gd = add3(ra.gd, mk3(d_val * v[0], d_val * v[1], d_val * v[2]));
+        }
         // d/d s_k = -g_p,k (R^T v)_k / s_k^2 = -g_p,k p_g,k / s_k
         v[3] = -(gp.x * p_g.x) * is[0];
         v[4] = -(gp.y * p_g.y) * is[1];
@@ -205,9 +258,21 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
     return geom;
 }
 
+#ifndef GRT_BWD_RAYS_TU
 template <bool MERGE>
 __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const BwdArgs b)
+#else
+// grt_backward_rays.hip: the same body; every ray's six floats are written once, by plain stores (zeros for a ray that is not
+// traced or whose upstream is zero).  GAUSS = false: nothing is scattered.
+template <bool MERGE, bool GAUSS>
+__global__ __launch_bounds__(kBlock) void k_backward_rays(const RenderArgs a, const BwdArgs b, const RayOut ro)
+#endif
 {
+#ifndef GRT_BWD_RAYS_TU
+    constexpr bool GAUSS = true, RAYS = false;
+#else
+    constexpr bool RAYS = true;
+#endif
     extern __shared__ uint32_t lds_stack[];
     uint32_t* stk = lds_stack + threadIdx.x;
     const uint32_t blk = xcd_swizzle(blockIdx.x, a.n_blocks, a.swizzle_chunk);
@@ -247,7 +312,22 @@ __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const B
         if (b.g_alpha) gA = b.g_alpha[idx];
         live = (gC.x != 0.0f) || (gC.y != 0.0f) || (gC.z != 0.0f) || (gA != 0.0f); // zero upstream: nothing is added
     }
+    RayAcc ra;
+    ra.go = ra.gd = ra.gdn = mk3(0, 0, 0);
+#ifdef GRT_BWD_RAYS_TU
+    // this lane has a ray of the buffer / a pixel of the window: its six floats are written whatever becomes of the wave
+    const bool has_out = (a.mode == 2) ? ((uint64_t)blk * kBlock + threadIdx.x < a.n_rays)
+                                       : ((a.x0 + (blk % a.nbx) * 16u + lx < a.x1) && (a.y0 + (blk / a.nbx) * 16u + ly < a.y1));
+    if (!__builtin_amdgcn_ballot_w64(live)) {
+        if (has_out) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) ro.rays[idx * 6 + k] = 0.0f;
+        }
+        return;
+    }
+#else
     if (!__builtin_amdgcn_ballot_w64(live)) return; // wave-uniform
+#endif
 
     const f3 dn = normalize3(d);
     const rayinv ri = mk_rayinv(o, d);
@@ -298,12 +378,15 @@ __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const B
                             rad = C;
                         } else {
                             ev = true;
-                            geom = event_terms(a, b, id, o, d, dn, L, T, hitAlpha, sub3(rad, C), g_rad, gAp, Tend, v);
+                            geom = event_terms<GAUSS, RAYS>(a, b, id, o, d, dn, L, T, hitAlpha, sub3(rad, C), g_rad, gAp, Tend, v, ra);
+#ifdef GRT_BWD_RAYS_TU
+                            geom = geom && (ro.scatter_geom != 0u);
+#endif
                         }
                         T *= (1.0f - hitAlpha);
                     }
                 }
-                if (pass) scatter<MERGE>(b.acc, ev, id, v, geom, b.want_sh != 0u, lane);
+                if (GAUSS && pass) scatter<MERGE>(b.acc, ev, id, v, geom, b.want_sh != 0u, lane);
             }
             if (act) {
                 if (kb.key[K - 1] == kKeyInvalid) act = false;
@@ -318,8 +401,18 @@ __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const B
             gAp = gA + dot3(gC, rad);                           // A = 1 - T_end enters through alpha and through rgbf
         }
     }
+#ifdef GRT_BWD_RAYS_TU
+    if (has_out) { // dloss/do = -sum m; dloss/dd = -sum d_val m + (I - dn dn^T) g_dn / |d|   (a lane that was not live holds zeros)
+        float* r = ro.rays + idx * 6;
+        r[0] = 0.0f - ra.go.x; r[1] = 0.0f - ra.go.y; r[2] = 0.0f - ra.go.z;
+        f3 pr = mk3(0, 0, 0);
+        if (live && a.p.sh_degree_max > 0u) pr = mul3s(sub3(ra.gdn, mul3s(dn, dot3(dn, ra.gdn))), 1.0f / length3(d));
+        r[3] = pr.x - ra.gd.x; r[4] = pr.y - ra.gd.y; r[5] = pr.z - ra.gd.z;
+    }
+#endif
 }
 
+#ifndef GRT_BWD_RAYS_TU
 // the context's gradient buffer -> the caller's arrays (added), and zeroed for the next call; one thread per float of a row
 __global__ __launch_bounds__(256) void k_bwd_flush(float* __restrict__ acc, uint64_t n_floats, float* __restrict__ g_pos, float* __restrict__ g_scale,
                                                    float* __restrict__ g_quat, float* __restrict__ g_opacity, float* __restrict__ g_sh)
@@ -346,6 +439,7 @@ __global__ __launch_bounds__(256) void k_bwd_flush_sh(float* __restrict__ acc_sh
     acc_sh[t] = 0.0f;
     g_sh[(t / kShHi) * 48 + 3 + (t % kShHi)] += v;
 }
+#endif
 
 } // namespace
 } // namespace grt
@@ -361,18 +455,12 @@ using namespace grt;
         }                                                                                             \
     } while (0)
 
-// a: mode, window / rays and n_blocks set by the caller
-static int backward_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf,
-                           const float* d_grad_alpha, const grt_gaussian_grads* g, void* stream, const char* fn)
+#ifndef GRT_BWD_RAYS_TU
+namespace grt {
+// The context's gradient buffers for n particles (hi: the higher-SH buffer as well), zeroed when new; a backward on another stream
+// than the last one's waits for that one's flush (the buffers belong to the context).
+int bwd_buffers(grt_ctx* c, uint64_t n, bool hi, hipStream_t s)
 {
-    const grt_ctx* sc = c->parent ? c->parent : c;
-    if (!d_rgbf || !d_alpha || !d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_rgbf, d_alpha, d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
-    const uint64_t n = sc->n;
-    const bool want_geom = g->pos || g->scale || g->quat || g->opacity;
-    if (a.n_blocks == 0 || n == 0 || sc->gbvh.root_ref == kNoRoot || (!want_geom && !g->sh)) { c->have_timing = false; return GRT_OK; } // nothing to differentiate
-    CHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const bool hi = p->sh_degree_max > 0 && g->sh;
     if (c->gacc_cap < n) {
         (void)hipFree(c->d_gacc); (void)hipFree(c->d_gacc_sh);
         c->d_gacc = c->d_gacc_sh = nullptr;
@@ -389,20 +477,14 @@ static int backward_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const
         CHK(c, hipMemsetAsync(c->d_gacc_sh, 0, n * kShHi * sizeof(float), s));
         c->gacc_sh_cap = n;
     }
-    // (the buffer belongs to the context: a backward on another stream than the last one's waits for that one's flush)
     if (c->bwd_pending && c->bwd_stream != s) CHK(c, hipStreamWaitEvent(s, c->ev_bwd, 0));
-    const uint32_t depth = std::max(sc->gbvh.height, 1u);
-    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
-    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
-    BwdArgs b;
-    b.pos = sc->d_pos; b.scale = sc->d_scale; b.quat = sc->d_quat; b.opacity = sc->d_opacity;
-    b.g_rgb = d_grad_rgbf; b.g_alpha = d_grad_alpha;
-    b.acc = c->d_gacc; b.acc_sh = hi ? c->d_gacc_sh : nullptr;
-    b.want_geom = want_geom ? 1u : 0u; b.want_sh = g->sh ? 1u : 0u;
-    auto fnk = c->opt_bwd_plain ? k_backward<false> : k_backward<true>;
-    CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(fnk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CHK(c, hipEventRecord(c->ev0, s));
-    hipLaunchKernelGGL(fnk, dim3(a.n_blocks), dim3(kBlock), lds, s, a, b);
+    return GRT_OK;
+}
+
+// The flush behind a backward kernel on s: the buffers added into the caller's arrays and zeroed; ev1 and the context's
+// "last backward" event recorded behind it.
+int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* g, hipStream_t s)
+{
     const uint64_t nf = n * kRow;
     hipLaunchKernelGGL(k_bwd_flush, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, c->d_gacc, nf, g->pos, g->scale, g->quat, g->opacity, g->sh);
     if (hi) {
@@ -417,6 +499,37 @@ static int backward_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const
     c->bwd_pending = true; c->bwd_stream = s;
     return GRT_OK;
 }
+} // namespace grt
+
+// a: mode, window / rays and n_blocks set by the caller
+static int backward_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf,
+                           const float* d_grad_alpha, const grt_gaussian_grads* g, void* stream, const char* fn)
+{
+    const grt_ctx* sc = c->parent ? c->parent : c;
+    if (!d_rgbf || !d_alpha || !d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_rgbf, d_alpha, d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
+    const uint64_t n = sc->n;
+    const bool want_geom = g->pos || g->scale || g->quat || g->opacity;
+    if (a.n_blocks == 0 || n == 0 || sc->gbvh.root_ref == kNoRoot || (!want_geom && !g->sh)) { c->have_timing = false; return GRT_OK; } // nothing to differentiate
+    CHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool hi = p->sh_degree_max > 0 && g->sh;
+    int rc = bwd_buffers(c, n, hi, s);
+    if (rc != GRT_OK) return rc;
+    const uint32_t depth = std::max(sc->gbvh.height, 1u);
+    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
+    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
+    BwdArgs b;
+    b.pos = sc->d_pos; b.scale = sc->d_scale; b.quat = sc->d_quat; b.opacity = sc->d_opacity;
+    b.g_rgb = d_grad_rgbf; b.g_alpha = d_grad_alpha;
+    b.acc = c->d_gacc; b.acc_sh = hi ? c->d_gacc_sh : nullptr;
+    b.want_geom = want_geom ? 1u : 0u; b.want_sh = g->sh ? 1u : 0u;
+    auto fnk = c->opt_bwd_plain ? k_backward<false> : k_backward<true>;
+    CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(fnk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CHK(c, hipEventRecord(c->ev0, s));
+    hipLaunchKernelGGL(fnk, dim3(a.n_blocks), dim3(kBlock), lds, s, a, b);
+    return bwd_flush(c, n, hi, g, s);
+}
+#endif
 
 static int backward_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
 {
@@ -443,6 +556,7 @@ static int backward_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const
     return GRT_OK;
 }
 
+#ifndef GRT_BWD_RAYS_TU
 extern "C" {
 
 int grt_backward(grt_ctx* c, const grt_params* p, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,
@@ -480,3 +594,4 @@ int grt_backward_rays(grt_ctx* c, const grt_params* p, const float* d_rays, uint
 }
 
 } // extern "C"
+#endif

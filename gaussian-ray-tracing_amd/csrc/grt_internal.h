@@ -445,3 +445,10 @@ struct grt_ctx {
     std::vector<float> upd_h_opacity, upd_h_s;
     hipEvent_t ev_upd0 = nullptr, ev_upd1 = nullptr;
 };
+
+namespace grt {
+// grt_backward.hip, shared with grt_backward_rays.hip: the context's gradient buffers made ready for a backward kernel on s, and the
+// flush kernels behind it (with the events that end a backward call).  GRT_OK or GRT_ERR_HIP (text in c->err).
+int bwd_buffers(grt_ctx* c, uint64_t n, bool hi, hipStream_t s);
+int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* g, hipStream_t s);
+}  // namespace grt

@@ -66,6 +66,11 @@ class GaussianGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "sh")]
 
 
+class BackwardOut(C.Structure):
+    """grt_backward_out (include/grt.h): the Gaussians' gradient arrays (or NULL) and the per-ray gradient array (or NULL)."""
+    _fields_ = [("gaussians", C.POINTER(GaussianGrads)), ("rays", C.c_void_p)]
+
+
 class UpdateInfo(C.Structure):
     """grt_update_info (include/grt.h): what grt_update_gaussians_device did."""
     _fields_ = [("mode_used", C.c_uint32), ("reason", C.c_uint32), ("device_ms", C.c_float), ("area_ratio", C.c_float)]
@@ -108,7 +113,7 @@ EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
     "grt_update_gaussians_device",
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
-    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_sync",
+    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -157,6 +162,8 @@ def lib():
         L.grt_render_rays_aux.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(AuxOut), vp]
         L.grt_backward.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
         L.grt_backward_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, C.POINTER(GaussianGrads), vp]
+        L.grt_backward_ex.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp, C.POINTER(BackwardOut), u32, u32, u32, u32, vp]
+        L.grt_backward_rays_ex.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, C.POINTER(BackwardOut), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -538,25 +545,59 @@ class Tracer:
                 raise GrtError(f"backward: gradient tensor '{k}' must be contiguous float32 of shape {(n,) + GRAD_SHAPES[k]}")
         return into, GaussianGrads(*(into[k].data_ptr() if k in into else None for k in ("pos", "scale", "quat", "opacity", "sh")))
 
-    def backward(self, params, rgbf, alpha, grad_rgbf, grad_alpha=None, window=None, into=None, groups=None):
+    def backward(self, params, rgbf, alpha, grad_rgbf, grad_alpha=None, window=None, into=None, groups=None, ray_grads=False):
         """grt_backward: gradients of a loss on the frame (rgbf [h][w][3], alpha [h][w] as render_aux wrote them; grad_rgbf / grad_alpha
         the loss's gradients with respect to them) with respect to the uploaded Gaussians -> dict of torch tensors pos, scale, quat,
-        opacity, sh (allocated zeroed, or accumulated into `into`).  Not bitwise reproducible (float atomics); include/grt.h."""
+        opacity, sh (allocated zeroed, or accumulated into `into`).  Not bitwise reproducible (float atomics); include/grt.h.
+        ray_grads: grt_backward_ex — the dict also holds "rays" [h][w][6] float32 (dloss/d eye, dloss/d unit direction per pixel; zero
+        outside the window), which IS bitwise reproducible; groups=[] with ray_grads is the rays-only call (no atomics, no buffer)."""
         dev = f"cuda:{self.device}"
-        into, ptrs = self._grad_buffers(into, groups, dev)
         x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
         keep = [x.contiguous() if x is not None else None for x in (rgbf, alpha, grad_rgbf, grad_alpha)]
+        if ray_grads:
+            into, out, hold = self._ex_buffers(into, groups, dev, (params.height, params.width, 6))
+            self._check(lib().grt_backward_ex(self._h, C.byref(params), *(x.data_ptr() if x is not None else None for x in keep), C.byref(out),
+                                              x0, y0, x1, y1, self._stream()))
+            return into
+        into, ptrs = self._grad_buffers(into, groups, dev)
         self._check(lib().grt_backward(self._h, C.byref(params), *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs),
                                        x0, y0, x1, y1, self._stream()))
         return into
 
-    def backward_rays(self, params, rays, rgbf, alpha, grad_rgbf, grad_alpha=None, into=None, groups=None):
-        """grt_backward_rays: as backward() for rays [n][6] (device, float32 o, d); rgbf [n][3], alpha [n] as render_rays_aux wrote them."""
-        into, ptrs = self._grad_buffers(into, groups, rays.device)
+    def backward_rays(self, params, rays, rgbf, alpha, grad_rgbf, grad_alpha=None, into=None, groups=None, ray_grads=False):
+        """grt_backward_rays: as backward() for rays [n][6] (device, float32 o, d); rgbf [n][3], alpha [n] as render_rays_aux wrote them.
+        ray_grads: grt_backward_rays_ex — "rays" [n][6] (dloss/do, dloss/dd) beside the groups."""
         keep = [x.contiguous() if x is not None else None for x in (rgbf, alpha, grad_rgbf, grad_alpha)]
+        if ray_grads:
+            into, out, hold = self._ex_buffers(into, groups, rays.device, (rays.shape[0], 6))
+            self._check(lib().grt_backward_rays_ex(self._h, C.byref(params), rays.data_ptr(), rays.shape[0],
+                                                   *(x.data_ptr() if x is not None else None for x in keep), C.byref(out), self._stream()))
+            return into
+        into, ptrs = self._grad_buffers(into, groups, rays.device)
         self._check(lib().grt_backward_rays(self._h, C.byref(params), rays.data_ptr(), rays.shape[0],
                                             *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs), self._stream()))
         return into
+
+    def _ex_buffers(self, into, groups, dev, ray_shape):
+        """The outputs of an extended backward call: the groups' tensors as _grad_buffers makes them (groups=[] or into={}: none, the
+        rays-only call) and the "rays" tensor: into["rays"] when given (WRITTEN, not added to; pixels outside a window keep what
+        they held), else a zeroed one."""
+        t = self._torch
+        rays_t = None
+        if into is not None:
+            into = dict(into)
+            rays_t = into.pop("rays", None)
+        if into is None and groups is not None and len(groups) == 0:
+            into = {}
+        into, ptrs = self._grad_buffers(into, groups, dev)
+        into = dict(into)
+        if rays_t is None:
+            rays_t = t.zeros(ray_shape, dtype=t.float32, device=dev)
+        elif tuple(rays_t.shape) != tuple(ray_shape) or rays_t.dtype != t.float32 or not rays_t.is_contiguous():
+            raise GrtError(f"backward: gradient tensor 'rays' must be contiguous float32 of shape {tuple(ray_shape)}")
+        into["rays"] = rays_t
+        out = BackwardOut(C.pointer(ptrs) if len(into) > 1 else None, into["rays"].data_ptr())
+        return into, out, ptrs
 
     def counters(self):
         c = Counters()

@@ -1,7 +1,8 @@
-"""torch.autograd wrapper of the renderer's backward pass (include/grt.h: grt_backward / grt_backward_rays).
+"""torch.autograd wrapper of the renderer's backward pass (include/grt.h: grt_backward / grt_backward_rays and their _ex forms).
 
     rgb, alpha = grt_torch.render(tracer, params, pos, scale, quat, opacity, sh)          # camera frame: [h][w][3], [h][w]
     rgb, alpha = grt_torch.render(tracer, params, pos, scale, quat, opacity, sh, rays)    # ray buffer:   [n][3],    [n]
+    rgb, alpha = grt_torch.render(tracer, params, pos, scale, quat, opacity, sh, camera=(eye, U, V, W))   # a camera to pose through
 
 The five tensors are the ACTIVATED attributes of grt_gaussians ([n][3] [n][3] [n][4] [n] [n][16][3]); the chain through exp /
 sigmoid / normalise is torch's, in the caller's own graph.  Leaves that all live on the tracer's GPU never touch the host: every
@@ -9,8 +10,10 @@ forward hands them to Tracer.update_device, which refits the BVH in hand while t
 (update="auto"; "refit" / "rebuild" force one), and their gradients stay on the device.  CPU leaves are uploaded from
 host arrays with a rebuild, as before; mixed leaves are moved to the device.  `tracer.last_update` holds what the last device update
 did.  Gaussian-only frames (a tracer with meshes set is refused by the backward).
+A `rays` tensor that requires grad receives its gradient ([n][6]: dloss/do, dloss/dd), and so do the four tensors of
+`camera=`; when none of the Gaussian leaves requires grad the backward runs the rays-only kernel (no atomics, no gradient buffer).
 The backward differentiates the scene the tracer HOLDS: it must run before the next upload to the same tracer (another
-grt_torch.render included), and raises GrtError otherwise.  Gradients with respect to rays / camera are not computed.  This is the only module of the package that imports torch at load.
+grt_torch.render included), and raises GrtError otherwise.  This is the only module of the package that imports torch at load.
 """
 import numpy as np
 import torch
@@ -18,9 +21,35 @@ import torch
 import grt
 
 
+def camera_rays(eye, U, V, W, width, height, fisheye=False):
+    """The raygen of a camera frame (get_ray / get_fisheye_ray of csrc/grt_device.h; shaders/tracer.cuh:115-165, U and V negated as
+    shaders/tracer.cu:35-45 hands them over) restated in torch, differentiable with respect to eye, U, V, W ([3] each).
+    Returns (rays [h][w][6] = eye, unit direction; valid [h][w] bool).  Fisheye pixels with r > 1 have no ray: valid False, zeros."""
+    dt, dev = W.dtype, W.device
+    ix = torch.arange(width, dtype=dt, device=dev)
+    iy = torch.arange(height, dtype=dt, device=dev)
+    dx = (2.0 * ((ix + 0.5) / float(width)) - 1.0)[None, :, None]
+    dy = (2.0 * ((iy + 0.5) / float(height)) - 1.0)[:, None, None]
+    nU, nV = -U, -V
+    if not fisheye:
+        d = (nU * dx + nV * dy) + W
+        valid = torch.ones((height, width), dtype=torch.bool, device=dev)
+    else:
+        s = dx * dx + dy * dy
+        valid = ~(torch.sqrt(s) > 1.0)[..., 0]
+        q = torch.sqrt(torch.clamp(2.0 - s, min=0.0))
+        d = (nU * (dx * q) + nV * (dy * q)) + W * (1.0 - s)
+    inv = 1.0 / torch.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+    d = d * inv[..., None]
+    rays = torch.cat([eye.to(dt).expand(height, width, 3), d], dim=-1)
+    return torch.where(valid[..., None], rays, torch.zeros_like(rays)), valid
+
+
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos, scale, quat, opacity, sh, tracer, params, rays, update):
+    def forward(ctx, pos, scale, quat, opacity, sh, rays, cam_rays, tracer, params, update):
+        # rays: a ray buffer [n][6], or None for a camera frame; cam_rays: camera_rays() of the frame's camera ([h][w][6]) — only the
+        # carrier of the per-pixel gradient (the frame itself is rendered from `params` by the tile kernel) —, or None
         leaves = (("pos", pos), ("scale", scale), ("quat", quat), ("opacity", opacity), ("sh", sh))
         if any(v.is_cuda for _, v in leaves):
             tracer.last_update = tracer.update_device({k: v for k, v in leaves}, params.alpha_min, update)
@@ -31,7 +60,13 @@ class _Render(torch.autograd.Function):
         if rays is None:
             out = tracer.render_aux(params, want_u8=False, want_f32=True, alpha=True, depth=False, count=False)
         else:
+            ctx.rays_like = (rays.device, rays.dtype)
+            rays = rays.detach()
+            if ctx.needs_input_grad[5]:
+                rays = rays.to(f"cuda:{tracer.device}", torch.float32).contiguous()
             out = tracer.render_rays_aux(params, rays, want_f32=True, alpha=True, depth=False, count=False)
+        if cam_rays is not None:
+            ctx.cam_like = (cam_rays.device, cam_rays.dtype)
         ctx.tracer, ctx.params, ctx.rays = tracer, params, rays
         ctx.like = tuple((t.device, t.dtype) for t in (pos, scale, quat, opacity, sh))
         ctx.save_for_backward(out["f32"], out["alpha"])
@@ -45,23 +80,44 @@ class _Render(torch.autograd.Function):
             raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
                                "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
         need = ctx.needs_input_grad[:5]
+        want_rays, want_cam = ctx.needs_input_grad[5], ctx.needs_input_grad[6]
         names = ("pos", "scale", "quat", "opacity", "sh")
         groups = [n for n, want in zip(names, need) if want]
-        if not groups:
-            return (None,) * 9
+        if not groups and not want_rays and not want_cam:
+            return (None,) * 10
         g_rgb = g_rgb.to(rgb.device, torch.float32).contiguous()
         g_alpha = g_alpha.to(rgb.device, torch.float32).contiguous() if g_alpha is not None else None
+        ray_grads = bool(want_rays or want_cam)  # (no group wanted: the rays-only kernel)
         if ctx.rays is None:
-            g = tr.backward(ctx.params, rgb, alpha, g_rgb, g_alpha, groups=groups)
+            g = tr.backward(ctx.params, rgb, alpha, g_rgb, g_alpha, groups=groups, ray_grads=ray_grads)
         else:
-            g = tr.backward_rays(ctx.params, ctx.rays, rgb, alpha, g_rgb, g_alpha, groups=groups)
+            g = tr.backward_rays(ctx.params, ctx.rays, rgb, alpha, g_rgb, g_alpha, groups=groups, ray_grads=ray_grads)
         out = tuple(g[n].to(dev, dt) if n in g else None for n, (dev, dt) in zip(names, ctx.like))
-        return out + (None, None, None, None)
+        g_rays = g["rays"].to(*ctx.rays_like) if want_rays else None
+        g_cam = g["rays"].to(*ctx.cam_like) if want_cam else None
+        return out + (g_rays, g_cam, None, None, None)
 
 
-def render(tracer, params, pos, scale, quat, opacity, sh, rays=None, update="auto"):
-    """(rgb, alpha) of the Gaussians given as torch tensors, differentiable with respect to all five (module docstring).
-    update: what a forward with CUDA leaves asks of Tracer.update_device — "auto", "refit" or "rebuild"."""
+def render(tracer, params, pos, scale, quat, opacity, sh, rays=None, update="auto", camera=None):
+    """(rgb, alpha) of the Gaussians given as torch tensors, differentiable with respect to all five (module docstring), to `rays`
+    when it requires grad, and to the four tensors of camera=(eye, U, V, W).
+    update: what a forward with CUDA leaves asks of Tracer.update_device — "auto", "refit" or "rebuild".
+    camera: the forward renders the camera frame of a copy of `params` with these four values written into it (the tile kernel, as
+    without camera=); the backward takes the per-pixel gradients with respect to the eye and the unit direction from grt_backward_ex
+    and pushes them through camera_rays() with torch's autograd.  torch's rays and the kernel's own may differ in the last unit of
+    the last place; that is irrelevant to a gradient — the rays of camera_rays() carry the gradient, they are never traced."""
     if update not in grt.UPDATE_MODES:
         raise ValueError(f"grt_torch.render: update must be one of {sorted(grt.UPDATE_MODES)}, not {update!r}")
-    return _Render.apply(pos, scale, quat, opacity, sh, tracer, params, rays, update)
+    cam_rays = None
+    if camera is not None:
+        if rays is not None:
+            raise ValueError("grt_torch.render: rays and camera exclude each other")
+        eye, U, V, W = camera
+        params = type(params).from_buffer_copy(params)
+        for name, t in (("eye", eye), ("U", U), ("V", V), ("W", W)):
+            v = t.detach().to("cpu", torch.float32).reshape(3)
+            for k in range(3):
+                getattr(params, name)[k] = float(v[k])
+        if any(t.requires_grad for t in camera):
+            cam_rays, _ = camera_rays(eye, U, V, W, params.width, params.height, bool(params.mode_fisheye))
+    return _Render.apply(pos, scale, quat, opacity, sh, rays, cam_rays, tracer, params, update)

@@ -400,7 +400,8 @@ GRT_API int grt_render_rays_aux(grt_ctx* ctx, const grt_params* p, const float* 
  *     dalpha_i/dopacity = r,  dalpha_i/dr = opacity  (when opacity r < 0.99);  dr/dp_g = -r p_g;  with v = mu - (o + d_val d), p_g = A v:
  *     d/dmu = A^T g_p,   d/ds_k = -g_p,k (R^T v)_k / s_k^2,   d/dR_jk = v_j g_p,k / s_k -> q through mat3_cast.
  * Gradients are with respect to the ACTIVATED attributes of grt_gaussians; the chain through exp / sigmoid / normalise is the
- * caller's.  Gradients with respect to rays / camera, and upstream gradients of depth / count, are not computed.
+ * caller's.  Gradients with respect to rays / camera come from grt_backward_ex below; upstream gradients of depth / count are
+ * not computed.
  *   d_rgbf, d_alpha          what the forward call wrote for the same parameters and window (grt_render_aux: d_rgbf and aux.alpha);
  *                            required.  (The kernel re-derives rad and T_end with a sweep of its own: DESIGN.md 5.8.)
  *   d_grad_rgbf, d_grad_alpha  upstream gradients, laid out like d_rgbf / alpha; d_grad_alpha may be NULL (= 0).
@@ -428,6 +429,42 @@ GRT_API int grt_backward(grt_ctx* ctx, const grt_params* p, const float* d_rgbf,
 GRT_API int grt_backward_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_rgbf,
                               const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,
                               const grt_gaussian_grads* grads, void* stream);
+/* ---- backward pass, extended: gradients with respect to the rays as well (pose refinement, learned ray generators) ----
+ * Same function, same rule: rgbf = rad * A, every discrete decision held fixed, p_g differentiated at fixed d_val (exact: d_val
+ * minimises |p_g|^2; where max(1e-6, .) binds, the stated convention).  The reference has no backward pass; the function is its
+ * raygen loop and trace() (shaders/tracer.cu:58-106, shaders/tracer.cuh:328-373), the response is computeResponse
+ * (shaders/tracer.cuh:187-214: p_g depends on the ray through o and d only), the colour's direction is SHToRadiance's
+ * (shaders/tracer.cuh:216-264).  With g_p, T_i, alpha_i, g_rad as above, for a ray (o, d), summed over its composited events i:
+ *     m_i        = A_i^T g_p,i                       (the vector added to pos of particle i; zero where the 0.99 clamp binds)
+ *     dloss/do   = - sum_i m_i
+ *     dloss/dd   = - sum_i d_val,i m_i  +  (I - dn dn^T) g_dn / |d|
+ *     g_dn       = sum_i sum_k (dY_k/dn)(dn) (sh_i,k . gL_i)
+ *     dn         = d/|d|
+ *     gL_i       = T_i alpha_i g_rad on the channels with L_i > 0
+ *     Y_k        = the polynomials of SHToRadiance, differentiated as polynomials in x, y, z (degree 0: no colour term)
+ * The hit geometry is a discrete decision and contributes nothing: which proxies are met, their key distances, t_min / t_max and
+ * the raygen guard.  A ray that is not traced (fisheye r > 1, |d| <= 0.1, a NaN direction, max_bounces = 0) or whose upstream is
+ * zero has gradient zero — exact zeros, never NaN.
+ *   out->gaussians   as `grads` of grt_backward (ADDED to), or NULL; a structure of five NULLs counts as NULL.
+ *   out->rays        [n][6] (grt_backward_rays_ex) or [h][w][6] (grt_backward_ex): (dloss/do, dloss/dd), WRITTEN, not added: every
+ *                    ray of the buffer and every pixel of the window receives its six floats; pixels outside the window are not
+ *                    written.  Camera frames: the gradient with respect to the eye and to the UNIT direction the raygen produced
+ *                    (shaders/tracer.cuh:115-165), through the (I - dn dn^T) / |d| above; the chain to U, V, W is the caller's.
+ *   out->rays NULL   exactly grt_backward / grt_backward_rays (which keep their own kernels).  Both NULL: GRT_ERR_INVALID.
+ * Every refusal of grt_backward holds.  The rays' gradients have no atomic in their path — a ray belongs to one lane, its events
+ * are summed in its own order and the six floats are stored once: two calls give them BIT FOR BIT, with and without the Gaussian
+ * output, merged or plain atomics.  A call without Gaussian output touches no gradient buffer and allocates none
+ * (grt_memory_info::slot_bytes is unchanged by it). */
+typedef struct {
+    const grt_gaussian_grads* gaussians; /* may be NULL */
+    float* rays;                         /* [n][6] or [h][w][6]; may be NULL */
+} grt_backward_out;
+GRT_API int grt_backward_ex(grt_ctx* ctx, const grt_params* p, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf,
+                            const float* d_grad_alpha, const grt_backward_out* out, uint32_t x0, uint32_t y0, uint32_t x1,
+                            uint32_t y1, void* stream);
+GRT_API int grt_backward_rays_ex(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_rgbf,
+                                 const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,
+                                 const grt_backward_out* out, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */

@@ -6,7 +6,9 @@
 Per workload (bench.py's scene and camera): grt_last_kernel_ms, median of 20 after 5, of (a) the per-lane forward kernel
 (GRT_OPT_KERNEL = 1), (b) the backward with the wave merge, (c) the backward with plain per-lane atomics
 (GRT_OPT_BWD_PLAIN_ATOMICS = 1), and (d) the default forward frame (tile kernel), all in this one process.  The upstream
-gradient is random normal on every pixel.
+gradient is random normal on every pixel.  Two more legs (profiles/r10_raygrad_timing.json holds C3 and C3:3):
+(e) grt_backward_ex with the ray gradients alone (no scatter, no flush) and (f) with the Gaussians' and the rays' together, beside
+(b), whose kernel is the one grt_backward has always run.
 """
 import json
 import os
@@ -60,7 +62,12 @@ def main():
         res["backward_plain_ms"] = median_ms(tr, lambda: tr.backward(p, fw["f32"], fw["alpha"], gC, gA, into=into))
         tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, 0)
         res["backward_colour_only_ms"] = median_ms(tr, lambda: tr.backward(p, fw["f32"], fw["alpha"], gC, gA, into={"sh": into["sh"]}))
+        rays_t = torch.zeros((h, w, 6), dtype=torch.float32, device=dev)
+        res["backward_rays_only_ms"] = median_ms(tr, lambda: tr.backward(p, fw["f32"], fw["alpha"], gC, gA, into={"rays": rays_t}, ray_grads=True))
+        res["backward_gauss_rays_ms"] = median_ms(tr, lambda: tr.backward(p, fw["f32"], fw["alpha"], gC, gA, into=dict(into, rays=rays_t), ray_grads=True))
         tr.check()
+        res["ratio_rays_only"] = res["backward_rays_only_ms"][0] / res["forward_perlane_ms"][0]
+        res["ratio_gauss_rays"] = res["backward_gauss_rays_ms"][0] / res["backward_merged_ms"][0]
         res["ratio_merged"] = res["backward_merged_ms"][0] / res["forward_perlane_ms"][0]
         res["ratio_plain"] = res["backward_plain_ms"][0] / res["forward_perlane_ms"][0]
         print(json.dumps(res), flush=True)
