@@ -17,6 +17,11 @@
 // sweeps, event_terms and scatter, the kernel named k_backward_rays<MERGE, GAUSS> with the per-ray output as a third argument, and
 // none of this unit's flush kernels and entry points.  Without the macro every addition below is compiled away: this unit's
 // assembly is what it was before them.
+// grt_backward_mesh.hip includes it with GRT_BWD_MESH_TU defined: event_terms, scatter and what they use, and no kernel, flush kernel
+// or entry point of this unit.
+#if !defined(GRT_BWD_RAYS_TU) && !defined(GRT_BWD_MESH_TU)
+#define GRT_BWD_MAIN_TU 1
+#endif
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -258,6 +263,7 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
     return geom;
 }
 
+#ifndef GRT_BWD_MESH_TU
 #ifndef GRT_BWD_RAYS_TU
 template <bool MERGE>
 __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const BwdArgs b)
@@ -411,8 +417,9 @@ __global__ __launch_bounds__(kBlock) void k_backward_rays(const RenderArgs a, co
     }
 #endif
 }
+#endif // !GRT_BWD_MESH_TU
 
-#ifndef GRT_BWD_RAYS_TU
+#ifdef GRT_BWD_MAIN_TU
 // the context's gradient buffer -> the caller's arrays (added), and zeroed for the next call; one thread per float of a row
 __global__ __launch_bounds__(256) void k_bwd_flush(float* __restrict__ acc, uint64_t n_floats, float* __restrict__ g_pos, float* __restrict__ g_scale,
                                                    float* __restrict__ g_quat, float* __restrict__ g_opacity, float* __restrict__ g_sh)
@@ -455,7 +462,7 @@ using namespace grt;
         }                                                                                             \
     } while (0)
 
-#ifndef GRT_BWD_RAYS_TU
+#ifdef GRT_BWD_MAIN_TU
 namespace grt {
 // The context's gradient buffers for n particles (hi: the higher-SH buffer as well), zeroed when new; a backward on another stream
 // than the last one's waits for that one's flush (the buffers belong to the context).
@@ -531,6 +538,7 @@ static int backward_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const
 }
 #endif
 
+#ifndef GRT_BWD_MESH_TU
 static int backward_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
 {
     if (!c) return GRT_ERR_INVALID;
@@ -555,8 +563,9 @@ static int backward_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const
     a->err_word = c->d_err;
     return GRT_OK;
 }
+#endif // !GRT_BWD_MESH_TU
 
-#ifndef GRT_BWD_RAYS_TU
+#ifdef GRT_BWD_MAIN_TU
 extern "C" {
 
 int grt_backward(grt_ctx* c, const grt_params* p, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,

@@ -113,7 +113,7 @@ EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
     "grt_update_gaussians_device",
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
-    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_sync",
+    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -164,6 +164,8 @@ def lib():
         L.grt_backward_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_backward_ex.argtypes = [vp, C.POINTER(Params), vp, vp, vp, vp, C.POINTER(BackwardOut), u32, u32, u32, u32, vp]
         L.grt_backward_rays_ex.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, C.POINTER(BackwardOut), vp]
+        L.grt_backward_mesh.argtypes = [vp, C.POINTER(Params), vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
+        L.grt_backward_rays_mesh.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -350,12 +352,18 @@ class Tracer:
         self._scene = scene  # keeps the parent alive as long as the view
         self.n_particles = 0  # of the last upload
         self.n_uploads = 0    # uploads so far (grt_torch: a backward refuses a scene that is no longer its forward's)
+        self._has_meshes = False  # set_meshes has set at least one face (a view reads its scene's: has_meshes)
         rc = lib().grt_create(C.byref(self._h), device) if scene is None else lib().grt_create_view(scene._h, C.byref(self._h))
         if rc != 0:
             raise GrtError(f"grt_create failed ({rc}): {lib().grt_last_error(None).decode()}")
 
     def view(self):
         return Tracer(scene=self)
+
+    @property
+    def has_meshes(self):
+        """Whether meshes are set on the scene this tracer renders (a view: its scene's)."""
+        return self._scene.has_meshes if self._scene is not None else self._has_meshes
 
     def _check(self, rc):
         if rc != 0:
@@ -416,7 +424,9 @@ class Tracer:
             f = np.ascontiguousarray(f, np.uint32)
             keep += [v, n, f]
             arr[i] = Mesh(v.ctypes.data, n.ctypes.data, len(v), f.ctypes.data, len(f))
+        self._has_meshes = False  # (a refused call leaves the context without meshes)
         self._check(lib().grt_set_meshes(self._h, arr, len(meshes)))
+        self._has_meshes = any(len(f) for f in keep[2::3])
 
     def update_meshes(self, meshes):
         """Same topology, new positions / normals: the mesh LBVH is re-fitted, not rebuilt."""
@@ -576,6 +586,26 @@ class Tracer:
         into, ptrs = self._grad_buffers(into, groups, rays.device)
         self._check(lib().grt_backward_rays(self._h, C.byref(params), rays.data_ptr(), rays.shape[0],
                                             *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs), self._stream()))
+        return into
+
+    def backward_mesh(self, params, grad_rgbf, grad_alpha=None, window=None, into=None, groups=None):
+        """grt_backward_mesh: backward() for a frame with meshes set (mirror, glass, normal; the meshes held fixed) — gradients of a
+        loss on the frame render_aux renders, with respect to the uploaded Gaussians.  No forward outputs are passed.  Without meshes
+        it differentiates the Gaussian-only frame, as backward() does."""
+        dev = f"cuda:{self.device}"
+        x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
+        keep = [x.contiguous() if x is not None else None for x in (grad_rgbf, grad_alpha)]
+        into, ptrs = self._grad_buffers(into, groups, dev)
+        self._check(lib().grt_backward_mesh(self._h, C.byref(params), *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs),
+                                            x0, y0, x1, y1, self._stream()))
+        return into
+
+    def backward_rays_mesh(self, params, rays, grad_rgbf, grad_alpha=None, into=None, groups=None):
+        """grt_backward_rays_mesh: backward_mesh() for rays [n][6] (device, float32 o, d), as render_rays_aux renders them."""
+        keep = [x.contiguous() if x is not None else None for x in (grad_rgbf, grad_alpha)]
+        into, ptrs = self._grad_buffers(into, groups, rays.device)
+        self._check(lib().grt_backward_rays_mesh(self._h, C.byref(params), rays.data_ptr(), rays.shape[0],
+                                                 *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs), self._stream()))
         return into
 
     def _ex_buffers(self, into, groups, dev, ray_shape):

@@ -1,4 +1,5 @@
-"""torch.autograd wrapper of the renderer's backward pass (include/grt.h: grt_backward / grt_backward_rays and their _ex forms).
+"""torch.autograd wrapper of the renderer's backward pass (include/grt.h: grt_backward / grt_backward_rays, their _ex forms, and
+grt_backward_mesh / grt_backward_rays_mesh for a tracer with meshes set).
 
     rgb, alpha = grt_torch.render(tracer, params, pos, scale, quat, opacity, sh)          # camera frame: [h][w][3], [h][w]
     rgb, alpha = grt_torch.render(tracer, params, pos, scale, quat, opacity, sh, rays)    # ray buffer:   [n][3],    [n]
@@ -9,7 +10,9 @@ sigmoid / normalise is torch's, in the caller's own graph.  Leaves that all live
 forward hands them to Tracer.update_device, which refits the BVH in hand while the particles move a little and rebuilds it otherwise
 (update="auto"; "refit" / "rebuild" force one), and their gradients stay on the device.  CPU leaves are uploaded from
 host arrays with a rebuild, as before; mixed leaves are moved to the device.  `tracer.last_update` holds what the last device update
-did.  Gaussian-only frames (a tracer with meshes set is refused by the backward).
+did.  A tracer with meshes set (mirror, glass, normal) renders its mesh frame with render_aux / render_rays_aux and differentiates it
+with respect to the five Gaussian tensors (the meshes are held fixed); gradients with respect to rays or camera do
+not pass through a bounce, so `rays` / `camera=` tensors that require grad raise ValueError on such a tracer.
 A `rays` tensor that requires grad receives its gradient ([n][6]: dloss/do, dloss/dd), and so do the four tensors of
 `camera=`; when none of the Gaussian leaves requires grad the backward runs the rays-only kernel (no atomics, no gradient buffer).
 The backward differentiates the scene the tracer HOLDS: it must run before the next upload to the same tracer (another
@@ -62,12 +65,13 @@ class _Render(torch.autograd.Function):
         else:
             ctx.rays_like = (rays.device, rays.dtype)
             rays = rays.detach()
-            if ctx.needs_input_grad[5]:
+            if ctx.needs_input_grad[5] or tracer.has_meshes:  # (the backward reads them on the device)
                 rays = rays.to(f"cuda:{tracer.device}", torch.float32).contiguous()
             out = tracer.render_rays_aux(params, rays, want_f32=True, alpha=True, depth=False, count=False)
         if cam_rays is not None:
             ctx.cam_like = (cam_rays.device, cam_rays.dtype)
         ctx.tracer, ctx.params, ctx.rays = tracer, params, rays
+        ctx.mesh = tracer.has_meshes
         ctx.like = tuple((t.device, t.dtype) for t in (pos, scale, quat, opacity, sh))
         ctx.save_for_backward(out["f32"], out["alpha"])
         return out["f32"], out["alpha"]
@@ -87,6 +91,12 @@ class _Render(torch.autograd.Function):
             return (None,) * 10
         g_rgb = g_rgb.to(rgb.device, torch.float32).contiguous()
         g_alpha = g_alpha.to(rgb.device, torch.float32).contiguous() if g_alpha is not None else None
+        if ctx.mesh:  # (render() has refused rays / camera that require grad)
+            if ctx.rays is None:
+                g = tr.backward_mesh(ctx.params, g_rgb, g_alpha, groups=groups)
+            else:
+                g = tr.backward_rays_mesh(ctx.params, ctx.rays, g_rgb, g_alpha, groups=groups)
+            return tuple(g[n].to(dev, dt) if n in g else None for n, (dev, dt) in zip(names, ctx.like)) + (None,) * 5
         ray_grads = bool(want_rays or want_cam)  # (no group wanted: the rays-only kernel)
         if ctx.rays is None:
             g = tr.backward(ctx.params, rgb, alpha, g_rgb, g_alpha, groups=groups, ray_grads=ray_grads)
@@ -109,6 +119,9 @@ def render(tracer, params, pos, scale, quat, opacity, sh, rays=None, update="aut
     if update not in grt.UPDATE_MODES:
         raise ValueError(f"grt_torch.render: update must be one of {sorted(grt.UPDATE_MODES)}, not {update!r}")
     cam_rays = None
+    if tracer.has_meshes and ((rays is not None and rays.requires_grad) or (camera is not None and any(t.requires_grad for t in camera))):
+        raise ValueError("grt_torch.render: meshes are set on this tracer, and gradients with respect to rays or camera are limited to "
+                         "Gaussian-only frames (they do not pass through a mirror or glass bounce); detach rays / camera, or clear the meshes")
     if camera is not None:
         if rays is not None:
             raise ValueError("grt_torch.render: rays and camera exclude each other")

@@ -409,8 +409,8 @@ GRT_API int grt_render_rays_aux(grt_ctx* ctx, const grt_params* p, const float* 
  *                            NULL (that group is not computed).  The gradients are ADDED to what the arrays hold: the caller zeroes them.
  * Fisheye pixels with r > 1 and pixels outside the window contribute nothing; so do rays the raygen loop does not trace
  * (|d| <= 0.1, max_bounces = 0).  Asynchronous on `stream` like grt_render; grt_last_kernel_ms reports the backward's device time.
- * Refused with GRT_ERR_INVALID (text in grt_last_error; the context stays usable): meshes set (the backward of mesh frames is future
- * work), GRT_OPT_COUNTERS = 1, no BVH, a NULL required pointer.  The sums are float atomics whose order of arrival differs from call
+ * Refused with GRT_ERR_INVALID (text in grt_last_error; the context stays usable): meshes set (mesh frames are differentiated by
+ * grt_backward_mesh / grt_backward_rays_mesh below), GRT_OPT_COUNTERS = 1, no BVH, a NULL required pointer.  The sums are float atomics whose order of arrival differs from call
  * to call: gradients are NOT bitwise reproducible between calls (tests compare within a tolerance measured for float32 evaluation).
  * A frame rendered after a backward is bit-identical to one rendered before it.  Backward calls of one context share its gradient
  * buffer: a call on another stream than the last one's waits for that one.  The buffer — 64 B per particle, and 180 B more per
@@ -451,7 +451,8 @@ GRT_API int grt_backward_rays(grt_ctx* ctx, const grt_params* p, const float* d_
  *                    written.  Camera frames: the gradient with respect to the eye and to the UNIT direction the raygen produced
  *                    (shaders/tracer.cuh:115-165), through the (I - dn dn^T) / |d| above; the chain to U, V, W is the caller's.
  *   out->rays NULL   exactly grt_backward / grt_backward_rays (which keep their own kernels).  Both NULL: GRT_ERR_INVALID.
- * Every refusal of grt_backward holds.  The rays' gradients have no atomic in their path — a ray belongs to one lane, its events
+ * Every refusal of grt_backward holds (meshes set among them: grt_backward_mesh / grt_backward_rays_mesh differentiate mesh frames,
+ * with respect to the Gaussians only).  The rays' gradients have no atomic in their path — a ray belongs to one lane, its events
  * are summed in its own order and the six floats are stored once: two calls give them BIT FOR BIT, with and without the Gaussian
  * output, merged or plain atomics.  A call without Gaussian output touches no gradient buffer and allocates none
  * (grt_memory_info::slot_bytes is unchanged by it). */
@@ -465,6 +466,47 @@ GRT_API int grt_backward_ex(grt_ctx* ctx, const grt_params* p, const float* d_rg
 GRT_API int grt_backward_rays_ex(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_rgbf,
                                  const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,
                                  const grt_backward_out* out, void* stream);
+/* ---- backward pass of mesh frames: mirror, glass and normal-shaded meshes in the scene, gradients with respect to the Gaussians ----
+ * The function that is differentiated is the raygen loop (shaders/tracer.cu:58-106) with the meshes held fixed.  A ray runs
+ * iterations s = 1..S.  Each has its own ray (o_s, d_s) — the camera's, or the one reflected / refracted at the last mesh hit —, its
+ * segment [t_min, tmax_s] (to the next mesh hit, or t_max) and a state from the mesh hit: Gaussian pass (a hit that bounces), last
+ * pass (a miss), terminate (GRT_NORMAL's hit).  THE TRANSMITTANCE RUNS ON ACROSS SEGMENTS (trace() starts at T = 1 - density, and the
+ * loop carries density): a ray has ONE event list with one running T, T_1 = 1, T_{i+1} = T_i (1 - alpha_i), cut into segments.  With
+ * alpha_i and L_i as above, on the ray of the event's own segment:
+ *     R_s = sum_{i in s} T_i alpha_i L_i,   T_end,s = T behind segment s,   D_s = 1 - T_end,s  (cumulative),   A_0 = B_0 = 0
+ *     Gaussian pass   C += R_s (1 - A_{s-1});          A_s = clamp(A_{s-1} + D_s, 0, 1);   B_s = clamp(B_{s-1} + D_s, 0, 1)
+ *     last pass       C += R_s D_s (1 - B_{s-1});      A_s = clamp(A_{s-1} + D_s, 0, 1)
+ *     terminate       C += R_s + ncol (1 - D_s);       A_s = A_{s-1} + D_s + (1 - D_s)        (ncol = (normal + 1) / 2)
+ *     rgbf = C,  alpha = A_S.
+ * Held fixed: everything grt_backward holds fixed, and the mesh hit, its normal and the next ray; the number of iterations
+ * (max_bounces, the 1000-iteration timeout, |d| > 0.1); whether each clamp binds at each step (derivative 0 through a binding
+ * clamp); T > minTransmittance at a segment's start.  With c_s = dC/dR_s — 1 - A_{s-1}, D_s (1 - B_{s-1}), 1 by state — and
+ * gD_s = dloss/dD_s at fixed R, for event i of segment s:
+ *     dloss/dalpha_i = c_s g_C.(T_i L_i)
+ *                      - 1/(1 - alpha_i) sum_{k behind i, in any segment} c_s(k) g_C.(T_k alpha_k L_k)
+ *                      + 1/(1 - alpha_i) sum_{j >= s} gD_j T_end,j
+ *     dloss/dL_i     = c_s T_i alpha_i g_C   (per channel, where L_i > 0; Y_k at d_s / |d_s|)
+ * and below alpha_i the chain of grt_backward with (o_s, d_s).  gD_s comes from the loop run backwards: a = g_A, b = 0, u^A_s / u^B_s
+ * = 1 where the clamp of step s does not bind, then from s = S down
+ *     last pass       gD_s = (g_C.R_s)(1 - B_{s-1}) + u^A_s a;   b -= (g_C.R_s) D_s;   a = u^A_s a
+ *     Gaussian pass   gD_s = u^A_s a + u^B_s b;                  a = u^A_s a - g_C.R_s;   b = u^B_s b
+ *     terminate       gD_s = -g_C.ncol.
+ * In closed form (what the kernel evaluates, with nothing stored per iteration: DESIGN.md 5.11): every iteration but the last is a
+ * Gaussian pass, and there B_s = A_s.  With e the last Gaussian pass before the clamp binds (all of them when it never does), sig =
+ * -(g_C.R_s*) when it binds at Gaussian pass s*, else g_A (no last pass), u^A_S g_A - (g_C.R_S) D_S (last pass), and Q_s = sum_{k <= s}
+ * g_C.R_k:  gD_s = sig - (Q_e - Q_s) for a Gaussian pass s <= e, 0 for one behind it.  Without meshes there is one last pass and
+ * this is grt_backward's function and derivative.
+ *   d_grad_rgbf, d_grad_alpha, grads, the window, the rays, stream    as for grt_backward / grt_backward_rays; gradients are ADDED, by
+ *                            original particle id.  No forward outputs are passed: the kernel re-derives what it needs.
+ * Refused as grt_backward refuses — GRT_OPT_COUNTERS = 1, no BVH, a NULL required pointer, a window outside the frame,
+ * sh_degree_max > 3, t_min <= 0 — but for meshes; a view differentiates its scene's meshes.  Gradients with respect to rays or camera
+ * through a bounce, to mesh vertices or normals, and upstream gradients of depth / count are not computed.  Float atomics, the
+ * context's gradient buffer and its flush are grt_backward's (GRT_OPT_BWD_PLAIN_ATOMICS applies); grt_last_kernel_ms reports kernel
+ * plus flush; a frame rendered after the call is bit-identical to one rendered before it. */
+GRT_API int grt_backward_mesh(grt_ctx* ctx, const grt_params* p, const float* d_grad_rgbf, const float* d_grad_alpha /* may be NULL */,
+                              const grt_gaussian_grads* grads, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_rays_mesh(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_rgbf,
+                                   const float* d_grad_alpha, const grt_gaussian_grads* grads, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */

@@ -9,6 +9,9 @@ Per workload (bench.py's scene and camera): grt_last_kernel_ms, median of 20 aft
 gradient is random normal on every pixel.  Two more legs (profiles/r10_raygrad_timing.json holds C3 and C3:3):
 (e) grt_backward_ex with the ray gradients alone (no scatter, no flush) and (f) with the Gaussians' and the rays' together, beside
 (b), whose kernel is the one grt_backward has always run.
+A workload with a mesh (C4: the mirror sphere; DESIGN.md 5.11, profiles/r11_mesh_bwd_timing.json) has its own legs, by the same
+method: (g) render_aux of the mesh frame — the per-lane aux kernel, the whole bounce loop per lane —, (h) grt_backward_mesh with the
+wave merge and (i) with plain atomics.
 """
 import json
 import os
@@ -48,6 +51,25 @@ def main():
         g = torch.Generator(device="cpu").manual_seed(1)
         gC = torch.randn((h, w, 3), generator=g).to(dev)
         gA = torch.randn((h, w), generator=g).to(dev)
+        mesh = bench.build_scene(grt, name)[2] if bench.WORKLOADS[name][5] else None
+        if mesh is not None:  # a mesh frame: the legs of DESIGN.md 5.11
+            p = grt.default_params(w, h, center, sh_degree=int(deg), mesh_type=grt.MIRROR, max_bounces=bench.WORKLOADS[name][6])
+            tr.set_meshes([mesh])
+            into = tr.backward_mesh(p, gC, gA)
+            tr.check()
+            res = {"workload": name, "sh_degree": int(deg), "n": n, "width": w, "height": h, "mesh_faces": int(len(mesh[2]))}
+            aux = lambda: tr.render_aux(p, want_u8=False, want_f32=True, depth=False, count=False)
+            res["forward_aux_perlane_ms"] = median_ms(tr, aux)
+            res["backward_mesh_ms"] = median_ms(tr, lambda: tr.backward_mesh(p, gC, gA, into=into))
+            tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, 1)
+            res["backward_mesh_plain_ms"] = median_ms(tr, lambda: tr.backward_mesh(p, gC, gA, into=into))
+            tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, 0)
+            tr.check()
+            res["ratio_mesh"] = res["backward_mesh_ms"][0] / res["forward_aux_perlane_ms"][0]
+            res["ratio_mesh_plain"] = res["backward_mesh_plain_ms"][0] / res["forward_aux_perlane_ms"][0]
+            print(json.dumps(res), flush=True)
+            tr.close()
+            continue
         fw = tr.render_aux(p, want_u8=False, want_f32=True, depth=False, count=False)
         out_f = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
         into = tr.backward(p, fw["f32"], fw["alpha"], gC, gA)
