@@ -44,10 +44,27 @@ FAULTS = ("density_not_carried", "segment_weight_left_out", "blocking_left_out",
 MEASURED_F32_MESH = {"mirror": 3.3e-5, "glass": 1.52e-4, "normal": 1.39e-5, "mirror_dense": 5.92e-6,
                      "mirror_sh3": 2.64e-5, "mirror_fisheye": 5.32e-5, "mirror_rays": 3.38e-5, "mirror_needles": 3.7e-2}
 
+# The same measurement on the scenes of mesh_grad_scenes.EDGE and SIZE (each with the worst group in the comment), re-measured by
+# tests/test_mesh_grad_check.py (EDGE) and by the GPU tests on the walks they hold.  These figures do not enter the tolerances of
+# the scenes above.
+MEASURED_F32_MESH_MORE = {"hall": 9.9e-5,              # pos
+                          "hall_cap4": 4.35e-4,        # pos
+                          "mirror_cuts": 1.14e-3,      # scale
+                          "few_glass": 8.94e-8,        # sh
+                          "crowded_mirror": 4.35e-5,   # scale
+                          "inside_glass": 6.01e-5,     # pos
+                          "zero_normals": 5.14e-5,     # pos
+                          "two_meshes": 2.6e-5,        # scale
+                          "ragged_mesh_rays": 4.95e-5, # scale
+                          "C4_sampled": 3.15e-4}       # quat
+FLOAT32_ROUNDING = 2.0 ** -23  # a GPU gradient is a float32 sum: it cannot be held to less than one rounding of a number the size of its scale
+
 
 def tol_of(name):
-    """The tolerance of a scene of MEASURED_F32_MESH: 4 x its own float32 figure."""
-    return 4 * MEASURED_F32_MESH[name]
+    """The tolerance of a scene: 4 x its own float32 figure; for the scenes of MEASURED_F32_MESH_MORE 4 x max(figure, 2^-23)."""
+    if name in MEASURED_F32_MESH:
+        return 4 * MEASURED_F32_MESH[name]
+    return 4 * max(MEASURED_F32_MESH_MORE[name], FLOAT32_ROUNDING)
 
 
 class MeshEvents:

@@ -1,7 +1,10 @@
 """CPU tests of the mesh frames' backward checker (tests/mesh_grad_check.py): every scene of tests/mesh_grad_scenes.py walked, proven
 against the pinned oracle and within its caps and conditions; the analytic gradients against torch.autograd of an independent
 float64 twin of the loop and against central differences; the closed form the kernel evaluates against the loop run backwards; the
-Gaussian-only case against grad_check.evaluate; the seeded faults; the float32 figures that set the GPU tests' tolerances."""
+Gaussian-only case against grad_check.evaluate; the seeded faults; the float32 figures that set the GPU tests' tolerances.
+The scenes of mesh_grad_scenes.EDGE come behind the four frames: each walked and proven, held to its caps and to the conditions
+that make it the edge it is named for, its figure re-measured; the closed form, autograd's twin and central differences on the
+deep loops of `hall` and on `mirror_cuts`; the seeded faults wherever a scene can show them."""
 import functools
 
 import numpy as np
@@ -284,3 +287,254 @@ def test_scene_tolerance_names_seeded_faults(name, fault):
     if len(untouched):  # a value where nothing may arrive is named too
         ghost["opacity"][untouched[0]] = 1e-30
         assert list(M.compare(ghost, s["want"], s["scale"], M.tol_of(name))) == ["opacity"]
+
+
+# ---- the edges: mesh_grad_scenes.EDGE ----
+def _last_rows(ev):
+    """the row of every ray's last step"""
+    return np.r_[np.nonzero(np.diff(ev.s_ray))[0], len(ev.s_ray) - 1]
+
+
+def edge_conditions(name, s, st):
+    """What makes each scene the edge it is named for: a recipe that stops reaching it fails here.  Returns a line for the log."""
+    ev, n, p = s["ev"], s["ev"].n_rays, s["op"]
+    sidx, mesh = st["step_index"], st["hit_mesh"]
+    if name == "hall":
+        deep = int((st["first_bind"] >= 3).sum())
+        free = int((mesh & (st["first_bind"] < 0)).sum())
+        n_steps = len(np.unique(st["ev_step"]))
+        assert st["steps"].max() >= 10 and n_steps >= 8 and deep >= 10 and free >= 100
+        return (f"up to {int(st['steps'].max())} steps, events in {n_steps} different steps, the A clamp first binds at step index >= 3 on {deep} rays "
+                f"(by index {np.bincount(st['first_bind'][st['first_bind'] >= 0]).tolist()}) and never on {free} mesh rays")
+    if name == "hall_cap4":
+        last = _last_rows(ev)
+        on_cap = (ev.s_state[last] == M.GAUSS) & (sidx[last] == p.max_bounces - 1)
+        with_ev = int((on_cap & st["rows_with"][last]).sum())
+        assert p.max_bounces == 4 and st["steps"].max() == 4 and with_ev >= 10
+        return f"{int(on_cap.sum())} rays end on the bounce cap (a Gaussian pass), {with_ev} of them with events in that last step"
+    if name == "mirror_cuts":
+        behind = int((np.bincount(ev.s_ray[st["rows_with"] & (sidx >= 1)], minlength=n) > 0).sum())
+        # bounced segments that start at T <= minTransmittance: no round runs on them, though proxies lie on them
+        spent = np.nonzero((sidx >= 1) & (st["T_start"] <= f32(p.min_transmittance)))[0]
+        assert not st["rows_with"][spent].any()
+        spent_rays = {int(ev.s_ray[r]) for r in spent if s["sc"].trace_gps(ev.s_o[r], ev.s_d[r], float(f32(p.t_min)), float(f32(p.t_max)))[0] > 0}
+        # last passes cut by t_max: transmittance left at the end, and proxies on the ray beyond t_max
+        T_end = 1.0 - np.asarray([float(x) for x in _end_density(ev, st)])
+        cut = [r for r in np.nonzero((ev.s_state == M.LAST) & (T_end > p.min_transmittance))[0]
+               if s["sc"].trace_gps(ev.s_o[r], ev.s_d[r], float(f32(p.t_max)), 1e5)[0] > 0]
+        # the same frame with the default cuts (walked, not proven again) composites more
+        d = S.build(name)
+        for k, v in (("t_min", 1e-3), ("t_max", 1e5), ("min_transmittance", 1e-3), ("alpha_min", 0.01)):
+            setattr(d["op"], k, v)
+        n_default = len(M.MeshWalker(d["parts"], d["op"], d["sc"], d["mesh"]).walk(d["rays"], d["live"], camera=True, prove=False).ray)
+        d["sc"].close()
+        assert behind >= 200 and len(spent_rays) >= 50 and len(cut) >= 50 and len(ev.ray) < n_default
+        return (f"{behind} rays with events behind the bounce, {len(spent_rays)} mesh rays whose bounced segment starts at T <= minTransmittance "
+                f"(no round, proxies on it), {len(cut)} last passes cut by t_max with transmittance left; {n_default} events with the default cuts")
+    if name == "few_glass":  # (that the mesh tree is the taller one is asserted where the trees are: tests/test_gpu_mesh_grad_edges.py)
+        assert len(s["parts"]) == 3 and len(s["mesh"][2]) >= 500 and mesh.sum() >= 100 and (st["ev_step"] >= 1).sum() >= 100
+        return f"{len(s['parts'])} Gaussians, {len(s['mesh'][2])} faces, {int(mesh.sum())} mesh rays"
+    if name == "crowded_mirror":
+        cl = (ev.pid < 600) & (sidx[ev.row] >= 1)
+        per = np.bincount(ev.row[cl], minlength=len(ev.s_ray))
+        assert cl.sum() >= 500 and (per >= 20).sum() >= 5
+        return (f"{int(cl.sum())} events on the 600 crowded Gaussians behind the bounce, {int((per >= 20).sum())} bounced segments with 20 or more "
+                f"of them (up to {int(per.max())})")
+    if name == "inside_glass":
+        assert mesh.sum() == s["n_traced"] == n and not (st["ev_step"] == 0).any() and (st["ev_step"] == 1).sum() >= 10000
+        assert (ev.s_state[sidx == 0] == M.GAUSS).all()
+        return f"all {n} rays hit the mesh at once, no event in step 0, {int((st['ev_step'] == 1).sum())} behind the refraction"
+    if name == "zero_normals":
+        assert not s["mesh"][1].any() and mesh.sum() >= 400 and st["steps"].max() == 1 and (ev.s_state[mesh[ev.s_ray]] == M.GAUSS).all()
+        return f"{int(mesh.sum())} mesh rays end on their Gaussian pass (the next direction is NaN)"
+    if name == "two_meshes":
+        zp = float(s["meshes"][0][0][0, 2])   # a step that starts on the plane / one that starts elsewhere on a mesh: the sphere
+        on_plane = np.abs(ev.s_o[:, 2] - zp) < 1e-4
+        both = (np.bincount(ev.s_ray[(sidx >= 1) & on_plane], minlength=n) > 0) & (np.bincount(ev.s_ray[(sidx >= 1) & ~on_plane], minlength=n) > 0)
+        assert len(s["meshes"]) == 2 and both.sum() >= 50
+        return f"{int(both.sum())} rays hit both meshes"
+    if name == "ragged_mesh_rays":
+        dead = ~S.traced(s["rays"], s["live"])
+        d = s["rays"][:, 3:]
+        with np.errstate(invalid="ignore"):
+            kinds = dict(zero=int((~d.any(1)).sum()), nan=int(np.isnan(d).any(1).sum()), short=int((dead & d.any(1) & ~np.isnan(d).any(1)).sum()))
+        zp = float(s["meshes"][0][0][0, 2])
+        behind = s["rays"][:, 2] < zp - 0.05
+        per_ray = np.bincount(ev.ray, minlength=n)
+        assert len(s["rays"]) == S.N_RAGGED == 46 * 64 + 57 and min(kinds.values()) >= 25 and dead.sum() == sum(kinds.values())
+        assert not dead[ev.ray].any() and not dead[ev.s_ray].any()        # untraced rays: no step, no event — exact zeros
+        for k in M.GROUPS:
+            z, _ = M.evaluate(s["parts"], ev, p.sh_degree_max, s["gC"] * dead[:, None], s["gA"] * dead)
+            assert not z[k].any(), k
+        assert behind.sum() >= 200 and (per_ray[behind] > 0).sum() >= 100 and (mesh & behind).sum() >= 10   # (the reversed ones meet its back)
+        assert (per_ray[-57:] > 0).sum() >= 40 and mesh.sum() >= 400
+        return (f"{int(dead.sum())} untraced rays {kinds}, {int(behind.sum())} origins behind the mirror ({int((per_ray[behind] > 0).sum())} with events, "
+                f"{int((mesh & behind).sum())} hit its back), the last 57 lanes hold {int(per_ray[-57:].sum())} events")
+    raise KeyError(name)
+
+
+def _end_density(ev, st):
+    """[R] float32: 1 - T at the end of every step, as the walk carries it"""
+    out = np.zeros(len(ev.s_ray), f32)
+    k = 0
+    for r in range(len(ev.s_ray)):
+        T = st["T_start"][r]
+        while k < len(ev.row) and ev.row[k] == r:
+            T = f32(T * f32(f32(1) - ev.alpha[k])); k += 1
+        out[r] = f32(f32(1) - T)
+    return out
+
+
+@pytest.mark.parametrize("name", S.EDGE)
+def test_edge_scene_is_proven_and_reaches_its_edge(name):
+    s = frame(name)  # (every segment and every ray proven, or CheckerMismatch)
+    ev, st = s["ev"], S.stats(s["ev"])
+    print(f"{name}: {len(ev.ray)} events on {s['n_traced']} traced rays of {len(s['rays'])}, events by step {np.bincount(st['ev_step']).tolist()}; "
+          f"{int(st['hit_mesh'].sum())} mesh rays, up to {int(st['steps'].max())} steps; {s['n_silenced']} rays silenced; walk {s['walk_seconds']:.1f} s")
+    assert s["n_silenced"] <= G.MAX_SILENCED * s["n_traced"]
+    assert len(ev.ray) > s["n_traced"]
+    print(f"{name}: {edge_conditions(name, s, st)}")
+    m32 = M.measure_f32(s["parts"], ev, s["op"].sh_degree_max, s["gCs"], s["gAs"])
+    fig = M.MEASURED_F32_MESH_MORE[name]
+    print(f"{name}: float32 evaluation, error / scale by group {({k: f'{v:.3e}' for k, v in m32.items()})}; recorded {fig:.3g}, "
+          f"tolerance {M.tol_of(name):.3g}")
+    assert fig / 2 < max(m32.values()) <= fig and M.tol_of(name) == 4 * max(fig, 2.0 ** -23)
+    for k, v in s["want"].items():
+        assert np.isfinite(v).all() and np.isfinite(s["scale"][k]).all(), k   # (zero normals, NaN directions: every gradient is finite)
+
+
+def test_closed_form_on_the_deep_loops():
+    """The kernel's closed form against the loop run backwards where its prefix sums hold more than one term and the clamp binds
+    deep in the loop (hall: steps 2 to 17), where the loop ends on the bounce cap (hall_cap4) and under the cuts (mirror_cuts):
+    gD on every ray, and the gradients with sum_{j >= s} gD_j T_end,j taken from the per-ray totals, to 1e-12 of the scale."""
+    for name in ("hall", "hall_cap4", "mirror_cuts"):
+        s = frame(name)
+        ev, deg = s["ev"], s["op"].sh_degree_max
+        P = G._attrs(s["parts"], np.float64)
+        _, a, _, L = M._event_quantities(P, ev, deg, np.float64)
+        worst, deep = 0.0, 0
+        for ri, es, rs in ev.by_ray():
+            nrow = rs.stop - rs.start
+            _, _, _, R, Tend = M._ray_forward(a[es], L[es], ev.row[es] - rs.start, nrow, np.float64)
+            D = 1 - Tend
+            state, uA, uB = ev.s_state[rs], ev.s_uA[rs], ev.s_uB[rs]
+            _, _, Bb, _ = M.step_weights(state, uA, uB, D, np.float64)
+            gc = s["gC"][ri].astype(np.float64)
+            q = R @ gc; qn = ev.s_ncol[rs].astype(np.float64) @ gc
+            ga = float(s["gA"][ri])
+            want = M.reverse_gD(state, uA, uB, D, Bb, q, ga, qn, np.float64)
+            unit = M.reverse_gD(state, uA, uB, D, Bb, np.abs(q), abs(ga), np.abs(qn), np.float64, absolute=True)
+            got = M.closed_form_gD(state, uA, D, Bb, q, ga, qn)
+            worst = max(worst, float(np.max(np.abs(got - want) / np.maximum(unit, 1e-300))))
+            deep += nrow >= 4
+        got, _ = M.evaluate(s["parts"], ev, deg, s["gCs"], s["gAs"], closed=True)
+        eos = M.error_over_scale(got, s["want"], s["scale"])
+        print(f"{name}: closed form vs reverse recurrence, worst gD difference / scale {worst:.2e} ({deep} rays of four steps or more); "
+              f"gradients from the per-ray totals, error / scale {max(eos.values()):.2e}")
+        assert worst < 1e-12 and not M.compare(got, s["want"], s["scale"], 1e-12), name
+        assert deep >= (10 if name != "mirror_cuts" else 0)  # (the scenes' own conditions: >= 10 rays bind at index >= 3 / end on the cap)
+
+
+def test_autograd_on_hall_and_mirror_cuts():
+    """torch.autograd of the float64 twin on the walk of `hall` (every ray: up to 17 steps) and on every sixth ray of `mirror_cuts`
+    (the twin indexes one tensor per event: its backward grows with the square of the event count), below 1e-9 of the scale."""
+    for name in ("hall", "mirror_cuts"):
+        s = frame(name)
+        ev, deg = s["ev"], s["op"].sh_degree_max
+        gC, gA = s["gC"].astype(np.float64), s["gA"].astype(np.float64)
+        if name == "mirror_cuts":
+            _, ev, deg, gC, gA = _few_rays(name, np.arange(0, len(s["rays"]), 6))
+            st = S.stats(ev)
+            spent = (st["step_index"] >= 1) & (st["T_start"] <= f32(s["op"].min_transmittance))
+            print(f"{name}, every sixth ray: {int((st['segs_with'] >= 2).sum())} rays with events behind the bounce, {int(spent.sum())} bounced segments "
+                  f"that start spent, {int(st['binds'].sum())} rays with a binding clamp")
+            assert (st["segs_with"] >= 2).sum() >= 20 and spent.sum() >= 20 and st["binds"].sum() >= 20
+        got, scale = M.evaluate(s["parts"], ev, deg, gC, gA)
+        P = {k: torch.tensor(np.ascontiguousarray(s["parts"][k]).astype(np.float64), requires_grad=True) for k in G.GROUPS}
+        loss = torch_loss(P, ev, deg, gC, gA)
+        loss.backward()
+        want = {k: v.grad.numpy() for k, v in P.items()}
+        eos = G.error_over_scale(got, want, scale)
+        print(f"{name}: {len(ev.ray)} events; analytic vs autograd, error / scale: {eos}")
+        assert not G.compare(got, want, scale, 1e-9), (name, eos)
+        assert all(np.abs(want[k]).max() > 0 for k in G.GROUPS)
+
+
+def _few_rays(name, pick):
+    """The scene walked on a few of its rays only (the others not live): (parts, ev, deg, gC, gA) for central differences."""
+    s = S.build(name)
+    live = np.zeros(len(s["rays"]), bool); live[pick] = True
+    ev = M.MeshWalker(s["parts"], s["op"], s["sc"], s["mesh"]).walk(s["rays"], live, camera=True)
+    s["sc"].close()
+    return s["parts"], ev, s["op"].sh_degree_max, s["gC"].astype(np.float64), s["gA"].astype(np.float64)
+
+
+@pytest.mark.parametrize("name", ["hall", "mirror_cuts"])
+def test_central_differences_on_hall_and_mirror_cuts(name):
+    """Central differences (long double, step 1e-6) of the forward function over the fixed event list, on four rays of the scene
+    that reach its edge — every parameter of every particle they meet —, below 1e-6 of the scale."""
+    s = frame(name)
+    st = S.stats(s["ev"])
+    sturdy = s["ev"].margin >= G.FRAGILE_REL
+    if name == "hall":   # the ray of the most steps, two more on which the clamp binds at step index >= 3, one that meets no mirror
+        longest = int(np.argmax(st["steps"] * sturdy))
+        deep = [r for r in np.nonzero((st["first_bind"] >= 3) & sturdy)[0] if r != longest][:2]
+        pick = np.r_[longest, deep, np.nonzero(~st["hit_mesh"] & sturdy & (st["segs_with"] > 0))[0][:1]].astype(np.int64)
+    else:                # two rays with events behind the bounce, one whose bounced segment starts spent, one that misses the mirror
+        n = s["ev"].n_rays
+        spent = np.zeros(n, bool)
+        spent[s["ev"].s_ray[(st["step_index"] >= 1) & (st["T_start"] <= f32(s["op"].min_transmittance))]] = True
+        pick = np.r_[np.nonzero((st["segs_with"] >= 2) & sturdy)[0][:2], np.nonzero(spent & sturdy)[0][:1],
+                     np.nonzero(~st["hit_mesh"] & sturdy & (st["segs_with"] > 0))[0][:1]]
+    assert len(pick) == 4
+    parts, ev, deg, gC, gA = _few_rays(name, pick)
+    st2 = S.stats(ev)
+    assert len(ev.ray) >= 20 and (st2["ev_step"] >= 1).any()
+    if name == "hall":
+        assert (st2["first_bind"] >= 3).sum() >= 2 and st2["steps"].max() >= 10
+    got, scale = M.evaluate(parts, ev, deg, gC, gA)
+    ld = np.longdouble
+    P0 = {k: np.ascontiguousarray(parts[k]).astype(ld) for k in G.GROUPS}
+
+    def loss(P):
+        rgb, alpha = M.composite(P, ev, deg, dt=ld)
+        return (rgb * gC.astype(ld)).sum() + (alpha * gA.astype(ld)).sum()
+
+    nb = (deg + 1) ** 2
+    fd = {k: np.zeros(P0[k].shape) for k in G.GROUPS}
+    hit = np.unique(ev.pid)
+    for k in G.GROUPS:
+        flat = P0[k].reshape(len(P0[k]), -1)
+        for i in hit:
+            for j in range(flat.shape[1] if k != "sh" else nb * 3):
+                x = flat[i, j]
+                h = ld(1e-6) * max(abs(x), ld(1e-2))
+                flat[i, j] = x + h; lp = loss(P0)
+                flat[i, j] = x - h; lm = loss(P0)
+                flat[i, j] = x
+                fd[k].reshape(len(P0[k]), -1)[i, j] = float((lp - lm) / (2 * h))
+    eos = G.error_over_scale(got, fd, scale)
+    print(f"{name}: rays {pick.tolist()}, {len(ev.ray)} events by step {np.bincount(st2['ev_step']).tolist()}, {len(hit)} particles hit; analytic vs "
+          f"central differences, error / scale: {eos}")
+    assert not G.compare(got, fd, scale, 1e-6), eos
+
+
+# What each seeded fault can change in an EDGE scene.  `inside_glass`: the first segment is empty — T is 1 and A, B are 0 when the one
+# segment with events starts, and no clamp binds on it: carrying the density, the blocking factor, the clamp and the later segments
+# change nothing; the segment's weight D (1 - B) does.  `zero_normals`: one step per ray, the mesh rays' a Gaussian pass of weight
+# 1 - A = 1: only the last passes of the other rays, through their weight D, show a fault.  Every other scene has events behind a
+# bounce with A, B > 0 and a clamp that binds on some rays: every fault shows.
+VISIBLE_EDGE = {n: M.FAULTS for n in S.EDGE}
+VISIBLE_EDGE["inside_glass"] = ("segment_weight_left_out",)
+VISIBLE_EDGE["zero_normals"] = ("segment_weight_left_out",)
+
+
+@pytest.mark.parametrize("name,fault", [(n, f) for n in S.EDGE for f in M.FAULTS])
+def test_edge_scene_tolerance_names_seeded_faults(name, fault):
+    s = frame(name)
+    got, _ = M.evaluate(s["parts"], s["ev"], s["op"].sh_degree_max, s["gCs"], s["gAs"], fault=fault)
+    bad = M.compare(got, s["want"], s["scale"], M.tol_of(name))
+    if fault in VISIBLE_EDGE[name]:
+        assert bad, (name, fault)
+    else:  # (the scene cannot show it: the faulty evaluation IS the gradient there, to rounding)
+        assert not M.compare(got, s["want"], s["scale"], 1e-12), (name, fault)
