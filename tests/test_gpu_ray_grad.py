@@ -45,7 +45,8 @@ def forward(tr, s):
 
 
 def run(tr, s, gC, gA, groups=None, window=None, ray_grads=True, fill=None):
-    """One forward + one backward -> numpy dict; "rays" flattened to [n][6].  fill: what the rays tensor holds before the call."""
+    """One forward + one backward -> numpy dict; "rays" flattened to [n][6].  fill: what the rays tensor holds before the call; gA None:
+    d_grad_alpha is NULL."""
     p = s["p"]
     fw, rays = forward(tr, s)
     into = None
@@ -57,10 +58,11 @@ def run(tr, s, gC, gA, groups=None, window=None, ray_grads=True, fill=None):
             into.update({k: torch.zeros((n,) + grt.GRAD_SHAPES[k], device=DEV) for k in (groups or grt.GRAD_SHAPES)})
     if s["camera"]:
         h, w = p.height, p.width
-        g = tr.backward(p, fw["f32"], fw["alpha"], _t(gC.reshape(h, w, 3)), _t(gA.reshape(h, w)), window=window, groups=groups, into=into,
-                        ray_grads=ray_grads)
+        g = tr.backward(p, fw["f32"], fw["alpha"], _t(gC.reshape(h, w, 3)), _t(gA.reshape(h, w)) if gA is not None else None, window=window,
+                        groups=groups, into=into, ray_grads=ray_grads)
     else:
-        g = tr.backward_rays(p, rays, fw["f32"], fw["alpha"], _t(gC), _t(gA), groups=groups, into=into, ray_grads=ray_grads)
+        g = tr.backward_rays(p, rays, fw["f32"], fw["alpha"], _t(gC), _t(gA) if gA is not None else None, groups=groups, into=into,
+                             ray_grads=ray_grads)
     tr.sync()
     tr.check()
     out = {k: v.cpu().numpy() for k, v in g.items()}
@@ -85,25 +87,35 @@ def assert_gauss_close(got, want, scale, what):
     assert not bad, (what, {k: (len(v), v[:5]) for k, v in bad.items()}, eos)
 
 
-@pytest.mark.parametrize("name", RS.NAMES)
-def test_ray_gradients_against_checker(tr, name):
-    s = RS.checked(name)
+def upload(tr, s):
+    """The scene on the tracer, its tree cut at the scene's own alpha_min (`cuts`: 0.03)."""
+    tr.upload(s["acts"], s.get("alpha_min", 0.01))
+
+
+def _frame_now(tr, s):
+    if s["camera"]:
+        return [x.cpu().numpy() for x in tr.render(s["p"], want_u8=True, want_f32=True)]
+    return [tr.render_rays_aux(s["p"], _t(s["rays"]), depth=False, count=False)["f32"].cpu().numpy()]
+
+
+def check_against_checker(tr, s, window=None):
+    """What every scene of ray_grad_scenes is held to (NAMES here, EDGE_NAMES in tests/test_gpu_ray_grad_edges.py): the rays-only
+    call, the combined call, a second call and plain atomics give the same bits; written, not added; exact zeros on every ray that
+    is not traced or has no upstream; the checker's values within tol_of(name); the Gaussians' gradients of the combined call and
+    of grt_backward within grad_check.TOL; the frame rendered afterwards is the one rendered before.
+    Returns (the rays-only call's [n][6], inside [n] bool: the rays of the window)."""
+    name = s["name"]
     RS.assert_caps(s)
     p = s["p"]
     n = len(s["rays"])
     gC, gA, want, scale, gwant, gscale = s["gCs"], s["gAs"], s["want"], s["scale"], s["gwant"], s["gscale"]
-    window = None
     inside = np.ones(n, bool)
-    if name == "sh3":  # a window: the pixels outside it keep the sentinel, and the Gaussians see the upstream of the window alone
-        window = RS.SH3_WINDOW
+    if window is not None:  # the pixels outside it keep the sentinel, and the Gaussians see the upstream of the window alone
         m = np.zeros((p.height, p.width), bool); m[window[1]:window[3], window[0]:window[2]] = True
         inside = m.reshape(-1)
         gwant, gscale = G.evaluate(s["parts"], s["ev"], s["rays"], s["deg"], gC * inside[:, None], gA * inside)
-    tr.upload(s["acts"])
-    if s["camera"]:
-        before = [x.cpu().numpy() for x in tr.render(p, want_u8=True, want_f32=True)]
-    else:
-        before = [tr.render_rays_aux(p, _t(s["rays"]), depth=False, count=False)["f32"].cpu().numpy()]
+    upload(tr, s)
+    before = _frame_now(tr, s)
     only = run(tr, s, gC, gA, groups=[], window=window, fill=SENTINEL)
     assert sorted(only) == ["rays"]
     both = run(tr, s, gC, gA, window=window, fill=SENTINEL)
@@ -116,15 +128,11 @@ def test_ray_gradients_against_checker(tr, name):
     # written, not added; nothing outside the window
     got = only["rays"]
     assert (got[~inside] == SENTINEL).all() and not (got[inside] == SENTINEL).any()
-    if name == "sh3":
-        assert (~inside).sum() == 40 * 28 - 34 * 21
     # the same bits: rays only vs combined, a second call, merged vs plain atomics
     for other, what in ((both, "combined"), (again, "second call"), (plain, "plain atomics")):
         assert np.array_equal(_bits(got), _bits(other["rays"])), what
-    # rays that are not traced (short, zero and NaN directions, fisheye r > 1): exact zeros, never NaN
+    # rays that are not traced (short, zero and NaN directions, fisheye r > 1) or have no upstream (off a sample): exact zeros, never NaN
     untraced = ~RS.S.traced(s["rays"], s["live"]) & inside
-    if name in ("rays", "ragged_rays", "fisheye"):
-        assert untraced.any()
     assert not np.isnan(got).any() and not _bits(got[untraced]).any()
     assert_rays_close(got[inside], s, want[inside], scale[inside], name)
     # the combined call's Gaussians, and grt_backward with the same inputs
@@ -133,17 +141,25 @@ def test_ray_gradients_against_checker(tr, name):
     old = run(tr, s, gC, gA, window=window, ray_grads=False)
     assert "rays" not in old
     assert_gauss_close(old, gwant, gscale, f"{name} grt_backward")
+    # a frame rendered afterwards equals the one rendered before
+    after = _frame_now(tr, s)
+    tr.check()
+    assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(before, after))
+    return got, inside
+
+
+@pytest.mark.parametrize("name", RS.NAMES)
+def test_ray_gradients_against_checker(tr, name):
+    s = RS.checked(name)
+    got, inside = check_against_checker(tr, s, window=RS.SH3_WINDOW if name == "sh3" else None)
+    if name == "sh3":
+        assert (~inside).sum() == 40 * 28 - 34 * 21
+    if name in ("rays", "ragged_rays", "fisheye"):
+        assert (~RS.S.traced(s["rays"], s["live"]) & inside).any()
     if name == "needles":
         assert tr.bvh_info()["n_primitives"] > tr.bvh_info()["n_proxies"]  # the tree holds pieces
     if name == "inside":
         assert s["ev"].clamp.any()  # clamped events add nothing to the ray either (the checker's m is zero there)
-    # a frame rendered afterwards equals the one rendered before
-    if s["camera"]:
-        after = [x.cpu().numpy() for x in tr.render(p, want_u8=True, want_f32=True)]
-    else:
-        after = [tr.render_rays_aux(p, _t(s["rays"]), depth=False, count=False)["f32"].cpu().numpy()]
-    tr.check()
-    assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(before, after))
 
 
 def test_sparse_upstream(tr):

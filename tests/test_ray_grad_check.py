@@ -2,8 +2,12 @@
 against central differences of grad_check.composite over the fixed event list, its seeded faults named, the float32 figures that set
 the GPU's tolerance measured again, and grt_torch.camera_rays against the oracle's raygen.
 
-Deviation from central differences (h = 1e-6, float64) as found when these scenes were fixed, as a fraction of the scene's largest
-gradient: rays 6.5e-9, ragged_rays 5.1e-9, sh3 1.8e-9, fisheye 1.0e-9, needles 4.6e-9, inside 3.1e-10."""
+Deviation from central differences (float64) as a fraction of the scene's largest gradient, at the step CD_STEP = 5e-7: rays 1.6e-9,
+ragged_rays 1.2e-9, sh3 4.5e-10, fisheye 4.1e-10, needles 1.1e-9, inside 1.2e-10; of EDGE_NAMES: cuts 1.1e-9, crowded 7.4e-10,
+blocks_frame 8.3e-10, blocks_rays 3.3e-9.  What remains is the difference quotient's own truncation error, not the formulas': it falls as
+h^2 (blocks_rays, worst ray |d| = 0.59, at h = 4e-6, 2e-6, 1e-6, 5e-7, 2.5e-7: 2.1e-7, 5.2e-8, 1.3e-8, 3.3e-9, 8.9e-10; the six older
+scenes stood at 6.5e-9 ... 3.1e-10 at h = 1e-6 and fall by 4 as well), whereas a wrong formula's deviation does not depend on h.  The
+step was 1e-6 until blocks_rays, whose 9 537 rays hold one on which the quotient alone is 1.3e-8 off; the bound, 1e-8, is unchanged."""
 import numpy as np
 import pytest
 import torch
@@ -14,6 +18,7 @@ import ray_grad_check as RG
 import ray_grad_scenes as RS
 
 f32 = np.float32
+CD_STEP = 5e-7
 
 
 def test_monomial_table_is_the_basis():
@@ -32,7 +37,7 @@ def test_monomial_table_is_the_basis():
     assert (RG.dbasis(dn, 3, absolute=True) >= np.abs(dY) - 1e-15).all()
 
 
-@pytest.mark.parametrize("name", RS.NAMES)
+@pytest.mark.parametrize("name", RS.NAMES + RS.EDGE_NAMES)
 def test_formulas_against_central_differences(name):
     s = RS.checked(name)
     RS.assert_caps(s)  # every walk proven against grto_trace (walk(prove=True)); the caps; the float32 figure in (figure / 2, figure]
@@ -40,7 +45,7 @@ def test_formulas_against_central_differences(name):
     assert not np.isnan(want).any()
     untraced = ~RS.S.traced(s["rays"], s["live"])
     assert not want[untraced].any() and not s["scale"][untraced].any()  # zero, NaN and short directions, fisheye r > 1: exact zeros
-    cd = RG.central_differences(s["parts"], s["ev"], s["rays"], s["deg"], s["gCs"], s["gAs"])
+    cd = RG.central_differences(s["parts"], s["ev"], s["rays"], s["deg"], s["gCs"], s["gAs"], h=CD_STEP)
     top = np.abs(want).max()
     dev = np.abs(cd - want).max() / top
     print(f"{name}: evaluate_rays against central differences: {dev:.2e} of the largest gradient ({top:.3g})")
@@ -48,9 +53,12 @@ def test_formulas_against_central_differences(name):
     if name == "rays":  # the buffer's directions are not unit vectors: the -d_val m term and the projection's 1 / |d| are exercised
         length = np.linalg.norm(s["rays"][:, 3:], axis=1)
         assert length.min() < 0.6 and length.max() > 1.9
+    if name.startswith("blocks_"):  # a sampled scene: the sample is what is traced, and every other ray is an exact zero above
+        assert s["n_traced"] == int(s["sample"].sum()) < len(s["rays"]) // 2
+        assert not s["gCs"][~s["sample"]].any() and not s["gAs"][~s["sample"]].any()
 
 
-@pytest.mark.parametrize("name", RS.NAMES)
+@pytest.mark.parametrize("name", RS.NAMES + RS.EDGE_NAMES)
 def test_seeded_faults_are_named(name):
     s = RS.checked(name)
     tol = RG.tol_of(name)
@@ -66,6 +74,28 @@ def test_seeded_faults_are_named(name):
     # the float32 evaluation itself passes at the GPU's tolerance
     got, _ = RG.evaluate_rays(s["parts"], s["ev"], s["rays"], s["deg"], s["gCs"], s["gAs"], dt=f32)
     assert not RG.compare(got, s["want"], s["scale"], tol)
+
+
+def test_the_cuts_are_another_function_of_the_ray():
+    """`cuts` with the default t_min, t_max, minTransmittance and alpha_min is another walk, and its ray gradients do not pass
+    compare against the scene's own: the GPU test that renders with the wrong cuts fails, it cannot pass by the scale's width."""
+    import grt
+    from common import to_oracle_params
+    s = RS.checked("cuts")
+    p = s["p"]
+    assert (p.t_min, p.t_max, p.minTransmittance, p.alpha_min) == tuple(f32(x) for x in (0.5, 3.0, 0.05, 0.03)) and s["alpha_min"] == 0.03
+    p0 = grt.default_params(p.width, p.height, grt.gaussian_center(s["acts"]["pos"]), sh_degree=1)
+    op0 = to_oracle_params(p0)
+    rays0, valid0 = O.camera_rays(op0)
+    assert np.array_equal(rays0.reshape(-1, 6), s["rays"])  # the same frame, the same rays
+    sc0 = O.Scene(s["parts"])
+    ev0 = G.walk(s["parts"], op0, sc0, s["rays"], valid0.reshape(-1))
+    sc0.close()
+    assert len(ev0.ray) > len(s["ev"].ray)
+    other, _ = RG.evaluate_rays(s["parts"], ev0, s["rays"], s["deg"], s["gCs"], s["gAs"])
+    bad = RG.compare(other, s["want"], s["scale"], RG.tol_of("cuts"))
+    print(f"cuts: {len(s['ev'].ray)} events with the cuts, {len(ev0.ray)} without; {len(bad.get('rays', []))} of {other.size} values differ")
+    assert "rays" in bad and len(bad["rays"]) > other.size // 2
 
 
 @pytest.mark.parametrize("fisheye", [False, True])
