@@ -1,425 +1,24 @@
 // grt_backward.hip — the backward pass of Gaussian-only frames (include/grt.h: grt_backward / grt_backward_rays):
 // gradients of a loss on (rgbf, alpha) with respect to the activated attributes of the Gaussians, discrete decisions held fixed.
 //
-// A translation unit of its own (kernels AND entry points).  One ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round
-// (grt_kround.h: the round trace_gaussians of grt_render.hip runs, without its watchdog and counters), twice per ray:
-//   sweep 0  re-derives rad and T_end (the forward's own arithmetic, so the same events in the same order);
-//   sweep 1  walks the same events again and forms every composited event's terms with S_i = rad - C_<=i.
-// (d_rgbf / d_alpha are not read: rad = rgbf / A and T_end = 1 - alpha lose what the float32 subtraction 1 - T lost — an absolute
-//  6e-8 on a T_end that may be 1e-5.  The second sweep costs a traversal and keeps the float32 error at the formulas' own.)
-// Scatter: float atomics into a context-owned AoS buffer (one 64-B row per particle: pos 3, scale 3, quat 4, opacity 1, degree-0
-// colour 3, pad 2; the 45 higher SH floats in a second buffer touched only at degree >= 1), added into the caller's arrays by one
-// streaming kernel that also zeroes the buffer.  MERGE: the lanes of the wave that composite the same particle in the same slot
-// of their k-buffers reduce their 14 values over the wave first (DPP inside rows of 16, v_readlane across) and 14 lanes add one
-// float each to the particle's contiguous row; a lane alone with its particle adds its own.  Only vector atomics write memory.
-//
-// grt_backward_rays.hip includes this file with GRT_BWD_RAYS_TU defined (the technique of grt_render_tile_aux.hip): the same two
-// sweeps, event_terms and scatter, the kernel named k_backward_rays<MERGE, GAUSS> with the per-ray output as a third argument, and
-// none of this unit's flush kernels and entry points.  Without the macro every addition below is compiled away: this unit's
-// assembly is what it was before them.
-// grt_backward_mesh.hip includes it with GRT_BWD_MESH_TU defined: event_terms, scatter and what they use, and no kernel, flush kernel
-// or entry point of this unit.
-#if !defined(GRT_BWD_RAYS_TU) && !defined(GRT_BWD_MESH_TU)
-#define GRT_BWD_MAIN_TU 1
-#endif
-#include <hip/hip_runtime.h>
-
+// The device text is grt_bwd.h; this unit instantiates k_backward<MERGE> from it and holds what exists once for the three backward
+// units: the flush kernels, the context's gradient buffers, and the host path every entry point takes (grt_internal.h: bwd_fill_args,
+// bwd_set_window, bwd_set_rays, bwd_launch).
 #include <algorithm>
 #include <cstring>
 #include <string>
 
-#include "grt_device.h"
-#include "grt_internal.h"
-#include "grt_kround.h"
+#include "grt_bwd.h"
 
 namespace grt {
 namespace {
 
-constexpr int K = 7;       // MaxNumHitPerTrace, shaders/tracer.cuh:11
-constexpr int kBlock = 256;
-static_assert(kBlock == kRoundBlock, "the per-lane stack stride of gps_round (grt_kround.h) is the launch block size");
-constexpr int kRow = 16;   // floats per particle row of the gradient buffer
-constexpr int kShHi = 45;  // floats per particle of the higher-SH buffer
-constexpr int kVals = 14;  // pos 3, scale 3, quat 4, opacity 1, sh0 3
-
-struct BwdArgs {
-    const float* pos;      // [n][3] by original id (the uploaded attributes)
-    const float* scale;    // [n][3]
-    const float* quat;     // [n][4]
-    const float* opacity;  // [n]
-    const float* g_rgb;    // upstream [pixels or rays][3]
-    const float* g_alpha;  // upstream [pixels or rays] or null
-    float* acc;            // [n][kRow]
-    float* acc_sh;         // [n][kShHi] (degree >= 1) or null
-    uint32_t want_geom;    // pos / scale / quat / opacity asked for (else their terms are not formed)
-    uint32_t want_sh;
-};
-
-// What one ray collects for grt_backward_ex (GRT_BWD_RAYS_TU): -dloss/do, the geometry part of dloss/dd, and g_dn (include/grt.h)
-struct RayAcc {
-    f3 go, gd, gdn;
-};
-#ifdef GRT_BWD_RAYS_TU
-struct RayOut {
-    float* rays;           // [pixels or rays][6], written
-    uint32_t scatter_geom; // the caller asked for pos / scale / quat / opacity (b.want_geom is set for the rays' sake as well)
-};
-// sum_k (dY_k/dn)(dn) c_k with c_k = sh_k . gL: the polynomials of sh_basis differentiated in x, y, z (deg >= 1)
-__device__ __forceinline__ f3 sh_basis_grad(const float* __restrict__ sh, f3 gL, f3 d, uint32_t deg)
-{
-#define GRT_SHC(i) (sh[(i) * 3] * gL.x + sh[(i) * 3 + 1] * gL.y + sh[(i) * 3 + 2] * gL.z)
-    const float x = d.x, y = d.y, z = d.z;
-    f3 g = mk3(-GRT_SH_C1 * GRT_SHC(3), -GRT_SH_C1 * GRT_SHC(1), GRT_SH_C1 * GRT_SHC(2));
-    if (deg < 2u) return g;
-    {
-        const float c4 = GRT_SH_C2_0 * GRT_SHC(4), c5 = GRT_SH_C2_1 * GRT_SHC(5), c6 = GRT_SH_C2_2 * GRT_SHC(6);
-        const float c7 = GRT_SH_C2_3 * GRT_SHC(7), c8 = GRT_SH_C2_4 * GRT_SHC(8);
-        g.x += ((c4 * y + c7 * z) + 2.0f * (c8 - c6) * x);
-        g.y += ((c4 * x + c5 * z) - 2.0f * (c8 + c6) * y);
-        g.z += ((c5 * y + c7 * x) + 4.0f * c6 * z);
-    }
-    if (deg < 3u) return g;
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
-    const float c9 = GRT_SH_C3_0 * GRT_SHC(9), c10 = GRT_SH_C3_1 * GRT_SHC(10), c11 = GRT_SH_C3_2 * GRT_SHC(11);
-    const float c12 = GRT_SH_C3_3 * GRT_SHC(12), c13 = GRT_SH_C3_4 * GRT_SHC(13), c14 = GRT_SH_C3_5 * GRT_SHC(14);
-    const float c15 = GRT_SH_C3_6 * GRT_SHC(15);
-    g.x += (((6.0f * c9 - 2.0f * c11) * xy + c10 * yz) + ((2.0f * c14 - 6.0f * c12) * xz + c13 * (4.0f * zz - 3.0f * xx - yy))) +
-           3.0f * c15 * (xx - yy);
-    g.y += (((3.0f * c9) * (xx - yy) + c10 * xz) + (c11 * (4.0f * zz - xx - 3.0f * yy) - (6.0f * c12 + 2.0f * c14) * yz)) -
-           (2.0f * c13 + 6.0f * c15) * xy;
-    g.z += ((c10 * xy + 8.0f * (c11 * yz + c13 * xz)) + (3.0f * c12) * (2.0f * zz - xx - yy)) + c14 * (xx - yy);
-#undef GRT_SHC
-    return g;
-}
-#endif
-
-// the basis of sh_radiance (grt_device.h): L = max(0, 0.5 + sum_k Y[k] sh_k); Y[1 .. (deg + 1)^2 - 1] are filled (deg >= 1)
-__device__ __forceinline__ void sh_basis(f3 d, uint32_t deg, float Y[16])
-{
-    const float x = d.x, y = d.y, z = d.z;
-    Y[1] = -GRT_SH_C1 * y; Y[2] = GRT_SH_C1 * z; Y[3] = -GRT_SH_C1 * x;
-    if (deg < 2u) return;
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
-    Y[4] = GRT_SH_C2_0 * xy; Y[5] = GRT_SH_C2_1 * yz; Y[6] = GRT_SH_C2_2 * (2.0f * zz - xx - yy);
-    Y[7] = GRT_SH_C2_3 * xz; Y[8] = GRT_SH_C2_4 * (xx - yy);
-    if (deg < 3u) return;
-    Y[9] = (GRT_SH_C3_0 * y) * (3.0f * xx - yy);
-    Y[10] = (GRT_SH_C3_1 * xy) * z;
-    Y[11] = (GRT_SH_C3_2 * y) * (4.0f * zz - xx - yy);
-    Y[12] = (GRT_SH_C3_3 * z) * (2.0f * zz - 3.0f * xx - 3.0f * yy);
-    Y[13] = (GRT_SH_C3_4 * x) * (4.0f * zz - xx - yy);
-    Y[14] = (GRT_SH_C3_5 * z) * (xx - yy);
-    Y[15] = (GRT_SH_C3_6 * x) * (xx - 3.0f * yy);
-}
-
-// sum over the wave of v (lanes outside `mine` hold 0), as a wave-uniform value
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));  // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));  // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)); // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true)); // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-// one lane's 14 values to its particle's row (geom: the 11 geometry / opacity values were formed; colour: the 3 colour values were)
-__device__ __forceinline__ void scatter_own(float* __restrict__ acc, uint32_t id, const float v[kVals], bool geom, bool colour)
-{
-    float* row = acc + (size_t)id * kRow;
-    if (geom) {
-#pragma unroll
-        for (int k = 0; k < 11; k++) atomicAdd(row + k, v[k]);
-    }
-    if (colour) {
-#pragma unroll
-        for (int k = 11; k < kVals; k++) atomicAdd(row + k, v[k]);
-    }
-}
-
-// Called by the WHOLE wave (ev: this lane has an event).  MERGE: lanes with the same particle add once.
-template <bool MERGE>
-__device__ __forceinline__ void scatter(float* __restrict__ acc, bool ev, uint32_t id, const float v[kVals], bool geom, bool colour, uint32_t lane)
-{
-    if (!MERGE) {
-        if (ev) scatter_own(acc, id, v, geom, colour);
-        return;
-    }
-    uint64_t todo = __builtin_amdgcn_ballot_w64(ev);
-    bool solo = false;
-    while (todo) { // wave-uniform
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, leader);
-        const bool mine = ev && id == lid;
-        const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
-        todo &= ~m;
-        if (__builtin_popcountll(m) == 1) { // alone with its particle: its own adds, once the groups are done
-            solo = solo || mine;
-            continue;
-        }
-        float out = 0.0f;
-#pragma unroll
-        for (int k = 0; k < kVals; k++) {
-            const float s = wave_sum(mine ? v[k] : 0.0f);
-            out = (lane == (uint32_t)k) ? s : out;
-        }
-        if (lane < (uint32_t)kVals && out != 0.0f) atomicAdd(acc + (size_t)lid * kRow + lane, out);
-    }
-    if (solo) scatter_own(acc, id, v, geom, colour);
-}
-
-// The terms of one composited event (sweep 1): v[0..13] = what it adds to pos 3, scale 3, quat 4, opacity, sh_0 3 of particle id (the
-// higher SH coefficients go to their buffer from here: one lane, one direction — nothing to merge across the wave).  T: the
-// transmittance before the event; S: what lies behind it (rad - C_<=i).  Returns whether the geometry / opacity terms were formed.
-// GAUSS: the Gaussians' gradients are wanted at all (else no atomic is in the text); RAYS: the event's part of the ray's gradient
-// goes to ra — m = A^T g_p (v[0..2]) to the origin, d_val m to the direction, the colour's direction derivative to g_dn.
-template <bool GAUSS, bool RAYS>
-__device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& b, uint32_t id, f3 o, f3 d, f3 dn, f3 L, float T, float hitAlpha,
-                                            f3 S, f3 g_rad, float gAp, float Tend, float v[kVals], RayAcc& ra)
-{
-    bool geom = false;
-    const float w = T * hitAlpha;
-    const float inv1 = 1.0f / (1.0f - hitAlpha);
-    const float dLda = (g_rad.x * (T * L.x - S.x * inv1) + g_rad.y * (T * L.y - S.y * inv1) + g_rad.z * (T * L.z - S.z * inv1)) +
-                       gAp * Tend * inv1;
-    // colour: dloss/dL_c = T alpha g_rad_c where L_c > 0
-    const f3 gL = mk3(L.x > 0.0f ? w * g_rad.x : 0.0f, L.y > 0.0f ? w * g_rad.y : 0.0f, L.z > 0.0f ? w * g_rad.z : 0.0f);
-    if (GAUSS && b.want_sh) {
-        v[11] = GRT_SH_C0 * gL.x; v[12] = GRT_SH_C0 * gL.y; v[13] = GRT_SH_C0 * gL.z;
-        if (a.p.sh_degree_max > 0u) { // the higher coefficients: one lane, one direction — no merge across the wave
-            float Y[16];
-            sh_basis(dn, a.p.sh_degree_max, Y);
-            float* hi = b.acc_sh + (size_t)id * kShHi;
-            const uint32_t nb = (a.p.sh_degree_max + 1u) * (a.p.sh_degree_max + 1u);
-#pragma unroll
-            for (uint32_t k = 1; k < 16; k++) {
-                if (k < nb) {
-                    atomicAdd(hi + (k - 1) * 3 + 0, Y[k] * gL.x);
-                    atomicAdd(hi + (k - 1) * 3 + 1, Y[k] * gL.y);
-                    atomicAdd(hi + (k - 1) * 3 + 2, Y[k] * gL.z);
-                }
-            }
-        }
-    }
-#ifdef GRT_BWD_RAYS_TU
-    if (RAYS && a.p.sh_degree_max > 0u) ra.gdn = add3(ra.gdn, sh_basis_grad(a.sh + (size_t)id * 48, gL, dn, a.p.sh_degree_max));
-#endif
-    if (b.want_geom && hitAlpha < 0.99f) { // (where the 0.99 clamp binds nothing goes into opacity or geometry)
-        geom = true;
-        const f3 mu = mk3(b.pos[id * 3], b.pos[id * 3 + 1], b.pos[id * 3 + 2]);
-        const float opac = b.opacity[id];
-        const float is[3] = {1.0f / b.scale[id * 3], 1.0f / b.scale[id * 3 + 1], 1.0f / b.scale[id * 3 + 2]};
-        const float qw = b.quat[id * 4], qx = b.quat[id * 4 + 1], qy = b.quat[id * 4 + 2], qz = b.quat[id * 4 + 3];
-        float Rg[9];
-        mat3_cast(qw, qx, qy, qz, Rg);
-        m33 A; // as k_gather_records forms it (grt_api.hip)
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.a[r * 3 + c] = is[r] * Rg[r * 3 + c];
-        }
-        // computeResponse (grt_device.h: response_from), keeping v = mu - (o + d_val d) and p_g = A v
-        const f3 o_g = matvec(A, sub3(o, mu));
-        const f3 d_g = matvec(A, d);
-        const float d_val = -dot3(o_g, d_g) / fmaxf(1e-6f, dot3(d_g, d_g));
-        const f3 vv = sub3(mu, add3(o, mul3s(d, d_val)));
-        const f3 p_g = matvec(A, vv);
-        const float r = exp_nonpos(-0.5f * dot3(p_g, p_g));
-        v[10] = dLda * r;                 // d alpha / d opacity = r
-        const float gr = -(dLda * opac) * r; // d r / d p_g = -r p_g
-        const f3 gp = mk3(gr * p_g.x, gr * p_g.y, gr * p_g.z);
-        // d/d mu = A^T g_p
-        v[0] = A.a[0] * gp.x + A.a[3] * gp.y + A.a[6] * gp.z;
-        v[1] = A.a[1] * gp.x + A.a[4] * gp.y + A.a[7] * gp.z;
-        v[2] = A.a[2] * gp.x + A.a[5] * gp.y + A.a[8] * gp.z;
-        if (RAYS) { // d p_g / d o = -A, d p_g / d d = -d_val A (at fixed d_val)
-            ra.go = add3(ra.go, mk3(v[0], v[1], v[2]));
-            ra.gd = add3(ra.gd, mk3(d_val * v[0], d_val * v[1], d_val * v[2]));
-        }
-        // d/d s_k = -g_p,k (R^T v)_k / s_k^2 = -g_p,k p_g,k / s_k
-        v[3] = -(gp.x * p_g.x) * is[0];
-        v[4] = -(gp.y * p_g.y) * is[1];
-        v[5] = -(gp.z * p_g.z) * is[2];
-        // d/d R_jk = v_j g_p,k / s_k, then through glm::mat3_cast
-        const float h[3] = {gp.x * is[0], gp.y * is[1], gp.z * is[2]};
-        const float vj[3] = {vv.x, vv.y, vv.z};
-        float G[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) G[j][k] = vj[j] * h[k];
-        }
-        v[6] = 2.0f * (((qz * (G[1][0] - G[0][1])) + (qy * (G[0][2] - G[2][0]))) + (qx * (G[2][1] - G[1][2])));
-        v[7] = 2.0f * ((((qy * (G[0][1] + G[1][0])) + (qz * (G[0][2] + G[2][0]))) + (qw * (G[2][1] - G[1][2]))) -
-                       2.0f * qx * (G[1][1] + G[2][2]));
-        v[8] = 2.0f * ((((qx * (G[0][1] + G[1][0])) + (qz * (G[1][2] + G[2][1]))) + (qw * (G[0][2] - G[2][0]))) -
-                       2.0f * qy * (G[0][0] + G[2][2]));
-        v[9] = 2.0f * ((((qx * (G[0][2] + G[2][0])) + (qy * (G[1][2] + G[2][1]))) + (qw * (G[1][0] - G[0][1]))) -
-                       2.0f * qz * (G[0][0] + G[1][1]));
-    }
-    return geom;
-}
-
-#ifndef GRT_BWD_MESH_TU
-#ifndef GRT_BWD_RAYS_TU
 template <bool MERGE>
 __global__ __launch_bounds__(kBlock) void k_backward(const RenderArgs a, const BwdArgs b)
-#else
-// grt_backward_rays.hip: the same body; every ray's six floats are written once, by plain stores (zeros for a ray that is not
-// traced or whose upstream is zero).  GAUSS = false: nothing is scattered.
-template <bool MERGE, bool GAUSS>
-__global__ __launch_bounds__(kBlock) void k_backward_rays(const RenderArgs a, const BwdArgs b, const RayOut ro)
-#endif
 {
-#ifndef GRT_BWD_RAYS_TU
-    constexpr bool GAUSS = true, RAYS = false;
-#else
-    constexpr bool RAYS = true;
-#endif
-    extern __shared__ uint32_t lds_stack[];
-    uint32_t* stk = lds_stack + threadIdx.x;
-    const uint32_t blk = xcd_swizzle(blockIdx.x, a.n_blocks, a.swizzle_chunk);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t lx = (wave & 1u) * 8u + (lane & 7u), ly = (wave >> 1) * 8u + (lane >> 3);
-    size_t idx = 0;
-    bool live = false;
-    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
-    if (a.mode == 2) { // ray buffer
-        const uint64_t i = (uint64_t)blk * kBlock + threadIdx.x;
-        if (i < a.n_rays) {
-            const float* r = a.rays + i * 6;
-            o = mk3(r[0], r[1], r[2]);
-            d = mk3(r[3], r[4], r[5]);
-            idx = (size_t)i;
-            live = true;
-        }
-    } else { // window of the full frame
-        const uint32_t px = a.x0 + (blk % a.nbx) * 16u + lx;
-        const uint32_t py = a.y0 + (blk / a.nbx) * 16u + ly;
-        idx = (size_t)py * a.p.width + px;
-        if ((px < a.x1) && (py < a.y1)) {
-            const f3 nU = mk3(-a.p.U[0], -a.p.U[1], -a.p.U[2]), nV = mk3(-a.p.V[0], -a.p.V[1], -a.p.V[2]);
-            const f3 W = mk3(a.p.W[0], a.p.W[1], a.p.W[2]);
-            live = true;
-            if (!a.p.mode_fisheye) get_ray(px, py, nU, nV, W, a.p.width, a.p.height, d);
-            else live = get_fisheye_ray(px, py, nU, nV, W, a.p.width, a.p.height, d);
-            o = mk3(a.p.eye[0], a.p.eye[1], a.p.eye[2]);
-        }
-    }
-    // the raygen loop's guard (shaders/tracer.cu:59): such a ray renders, and differentiates, to nothing
-    live = live && (length3(d) > 0.1f) && (a.p.max_bounces > 0u) && (a.root_ref != kNoRoot);
-    f3 gC = mk3(0, 0, 0);
-    float gA = 0.0f;
-    if (live) {
-        gC = mk3(b.g_rgb[idx * 3], b.g_rgb[idx * 3 + 1], b.g_rgb[idx * 3 + 2]);
-        if (b.g_alpha) gA = b.g_alpha[idx];
-        live = (gC.x != 0.0f) || (gC.y != 0.0f) || (gC.z != 0.0f) || (gA != 0.0f); // zero upstream: nothing is added
-    }
-    RayAcc ra;
-    ra.go = ra.gd = ra.gdn = mk3(0, 0, 0);
-#ifdef GRT_BWD_RAYS_TU
-    // this lane has a ray of the buffer / a pixel of the window: its six floats are written whatever becomes of the wave
-    const bool has_out = (a.mode == 2) ? ((uint64_t)blk * kBlock + threadIdx.x < a.n_rays)
-                                       : ((a.x0 + (blk % a.nbx) * 16u + lx < a.x1) && (a.y0 + (blk / a.nbx) * 16u + ly < a.y1));
-    if (!__builtin_amdgcn_ballot_w64(live)) {
-        if (has_out) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) ro.rays[idx * 6 + k] = 0.0f;
-        }
-        return;
-    }
-#else
-    if (!__builtin_amdgcn_ballot_w64(live)) return; // wave-uniform
-#endif
-
-    const f3 dn = normalize3(d);
-    const rayinv ri = mk_rayinv(o, d);
-    const float epsT = 1e-9f;
-    const float t_max = a.p.t_max;
-    const float t_hi = t_max + epsT;
-    const float minT = a.p.minTransmittance;
-    const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
-    KBuf<K> kb;
-    Cnt cnt; // (dead: no counters, no watchdog)
-
-    // ---- two sweeps over the same events through ONE call site of the traversal (every lane of the wave in step: the scatter of
-    //      sweep 1 is wave-cooperative).  Sweep 0: rad and T_end, trace() as the forward runs it (shaders/tracer.cuh:328-373);
-    //      sweep 1: every composited event's terms ----
-    f3 rad = mk3(0, 0, 0), g_rad = mk3(0, 0, 0);
-    float Tend = 1.0f, gAp = 0.0f;
-#pragma unroll 1
-    for (int pass = 0; pass < 2; pass++) {
-        float T = 1.0f, lastT = a.p.t_min;
-        uint64_t last_key = key0;
-        f3 C = mk3(0, 0, 0);
-        bool act = live && (lastT <= t_max) && (T > minT);
-        while (__builtin_amdgcn_ballot_w64(act)) {
-            if (act) {
-                gps_round<false, false, K>(a, stk, o, d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
-                if (kb.key[0] == kKeyInvalid) act = false;
-            }
-#pragma unroll 1
-            for (int i = 0; i < K; i++) {
-                bool ev = false, geom = false;
-                uint32_t id = 0;
-                float v[kVals];
-#pragma unroll
-                for (int k = 0; k < kVals; k++) v[k] = 0.0f;
-                uint64_t key = kKeyInvalid;
-                float hitAlpha = 0.0f;
-#pragma unroll
-                for (int j = 0; j < K; j++) {
-                    if (j == i) { key = kb.key[j]; hitAlpha = kb.alpha[j]; }
-                }
-                if (act && key != kKeyInvalid && T > minT) {
-                    lastT = fmaxf(key_t(key), lastT);
-                    if (a.p.alpha_min < hitAlpha) {
-                        id = key_id(key);
-                        const f3 L = event_radiance(a, id, dn);
-                        C = add3(C, mul3s(mul3s(L, T), hitAlpha)); // (sweep 0: this is rad, term by term as the forward adds it)
-                        if (pass == 0) {
-                            rad = C;
-                        } else {
-                            ev = true;
-                            geom = event_terms<GAUSS, RAYS>(a, b, id, o, d, dn, L, T, hitAlpha, sub3(rad, C), g_rad, gAp, Tend, v, ra);
-#ifdef GRT_BWD_RAYS_TU
-                            geom = geom && (ro.scatter_geom != 0u);
-#endif
-                        }
-                        T *= (1.0f - hitAlpha);
-                    }
-                }
-                if (GAUSS && pass) scatter<MERGE>(b.acc, ev, id, v, geom, b.want_sh != 0u, lane);
-            }
-            if (act) {
-                if (kb.key[K - 1] == kKeyInvalid) act = false;
-                else last_key = kb.key[K - 1];
-                act = act && (lastT <= t_max) && (T > minT);
-            }
-        }
-        if (pass == 0) {
-            Tend = T;
-            const float dens = clampf(1.0f - Tend, 0.0f, 1.0f); // grt_aux_out::alpha
-            g_rad = mul3s(gC, dens);                            // rgbf = rad * A
-            gAp = gA + dot3(gC, rad);                           // A = 1 - T_end enters through alpha and through rgbf
-        }
-    }
-#ifdef GRT_BWD_RAYS_TU
-    if (has_out) { // dloss/do = -sum m; dloss/dd = -sum d_val m + (I - dn dn^T) g_dn / |d|   (a lane that was not live holds zeros)
-        float* r = ro.rays + idx * 6;
-        r[0] = 0.0f - ra.go.x; r[1] = 0.0f - ra.go.y; r[2] = 0.0f - ra.go.z;
-        f3 pr = mk3(0, 0, 0);
-        if (live && a.p.sh_degree_max > 0u) pr = mul3s(sub3(ra.gdn, mul3s(dn, dot3(dn, ra.gdn))), 1.0f / length3(d));
-        r[3] = pr.x - ra.gd.x; r[4] = pr.y - ra.gd.y; r[5] = pr.z - ra.gd.z;
-    }
-#endif
+    backward_body<MERGE, true, false>(a, b, RayOut{});
 }
-#endif // !GRT_BWD_MESH_TU
 
-#ifdef GRT_BWD_MAIN_TU
 // the context's gradient buffer -> the caller's arrays (added), and zeroed for the next call; one thread per float of a row
 __global__ __launch_bounds__(256) void k_bwd_flush(float* __restrict__ acc, uint64_t n_floats, float* __restrict__ g_pos, float* __restrict__ g_scale,
                                                    float* __restrict__ g_quat, float* __restrict__ g_opacity, float* __restrict__ g_sh)
@@ -446,7 +45,6 @@ __global__ __launch_bounds__(256) void k_bwd_flush_sh(float* __restrict__ acc_sh
     acc_sh[t] = 0.0f;
     g_sh[(t / kShHi) * 48 + 3 + (t % kShHi)] += v;
 }
-#endif
 
 } // namespace
 } // namespace grt
@@ -462,11 +60,9 @@ using namespace grt;
         }                                                                                             \
     } while (0)
 
-#ifdef GRT_BWD_MAIN_TU
-namespace grt {
 // The context's gradient buffers for n particles (hi: the higher-SH buffer as well), zeroed when new; a backward on another stream
 // than the last one's waits for that one's flush (the buffers belong to the context).
-int bwd_buffers(grt_ctx* c, uint64_t n, bool hi, hipStream_t s)
+static int bwd_buffers(grt_ctx* c, uint64_t n, bool hi, hipStream_t s)
 {
     if (c->gacc_cap < n) {
         (void)hipFree(c->d_gacc); (void)hipFree(c->d_gacc_sh);
@@ -490,7 +86,7 @@ int bwd_buffers(grt_ctx* c, uint64_t n, bool hi, hipStream_t s)
 
 // The flush behind a backward kernel on s: the buffers added into the caller's arrays and zeroed; ev1 and the context's
 // "last backward" event recorded behind it.
-int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* g, hipStream_t s)
+static int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* g, hipStream_t s)
 {
     const uint64_t nf = n * kRow;
     hipLaunchKernelGGL(k_bwd_flush, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, c->d_gacc, nf, g->pos, g->scale, g->quat, g->opacity, g->sh);
@@ -506,48 +102,19 @@ int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* g, hipS
     c->bwd_pending = true; c->bwd_stream = s;
     return GRT_OK;
 }
-} // namespace grt
 
-// a: mode, window / rays and n_blocks set by the caller
-static int backward_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf,
-                           const float* d_grad_alpha, const grt_gaussian_grads* g, void* stream, const char* fn)
-{
-    const grt_ctx* sc = c->parent ? c->parent : c;
-    if (!d_rgbf || !d_alpha || !d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_rgbf, d_alpha, d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
-    const uint64_t n = sc->n;
-    const bool want_geom = g->pos || g->scale || g->quat || g->opacity;
-    if (a.n_blocks == 0 || n == 0 || sc->gbvh.root_ref == kNoRoot || (!want_geom && !g->sh)) { c->have_timing = false; return GRT_OK; } // nothing to differentiate
-    CHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const bool hi = p->sh_degree_max > 0 && g->sh;
-    int rc = bwd_buffers(c, n, hi, s);
-    if (rc != GRT_OK) return rc;
-    const uint32_t depth = std::max(sc->gbvh.height, 1u);
-    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
-    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
-    BwdArgs b;
-    b.pos = sc->d_pos; b.scale = sc->d_scale; b.quat = sc->d_quat; b.opacity = sc->d_opacity;
-    b.g_rgb = d_grad_rgbf; b.g_alpha = d_grad_alpha;
-    b.acc = c->d_gacc; b.acc_sh = hi ? c->d_gacc_sh : nullptr;
-    b.want_geom = want_geom ? 1u : 0u; b.want_sh = g->sh ? 1u : 0u;
-    auto fnk = c->opt_bwd_plain ? k_backward<false> : k_backward<true>;
-    CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(fnk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CHK(c, hipEventRecord(c->ev0, s));
-    hipLaunchKernelGGL(fnk, dim3(a.n_blocks), dim3(kBlock), lds, s, a, b);
-    return bwd_flush(c, n, hi, g, s);
-}
-#endif
+namespace grt {
 
-#ifndef GRT_BWD_MESH_TU
-static int backward_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
+int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn)
 {
     if (!c) return GRT_ERR_INVALID;
     if (!p) { c->err = std::string(fn) + ": null parameters"; return GRT_ERR_INVALID; }
     const grt_ctx* sc = c->parent ? c->parent : c;
     if (!sc->built) { c->err = std::string(fn) + ": grt_build_bvh has not been called after the last upload"; return GRT_ERR_INVALID; }
-    if (sc->n_faces) { c->err = std::string(fn) + ": meshes are set (the backward of mesh frames is future work)"; return GRT_ERR_INVALID; }
+    if (!mesh && sc->n_faces) { c->err = std::string(fn) + ": meshes are set (grt_backward_mesh / grt_backward_rays_mesh differentiate mesh frames)"; return GRT_ERR_INVALID; }
     if (c->opt_counters) { c->err = std::string(fn) + ": GRT_OPT_COUNTERS = 1 (the backward kernel is not instrumented)"; return GRT_ERR_INVALID; }
     if (p->sh_degree_max > 3) { c->err = std::string(fn) + ": sh_degree_max must be 0..3"; return GRT_ERR_INVALID; }
+    if (mesh && (p->type < 0 || p->type > 2)) { c->err = std::string(fn) + ": type must be MIRROR/NORMAL/GLASS"; return GRT_ERR_INVALID; }
     if (!(p->t_min > 0.0f)) { c->err = std::string(fn) + ": t_min must be > 0"; return GRT_ERR_INVALID; }
     memset(a, 0, sizeof(*a));
     a->p = *p;
@@ -559,48 +126,119 @@ static int backward_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const
     a->color0 = sc->d_color0;
     a->sh = sc->d_sh;
     a->mroot = kNoRoot;
+    if (mesh) { // the mesh side, as the per-lane aux launch has it (grt_api.hip: fill_common)
+        a->mnodes = sc->mbvh.nodes;
+        a->tri = sc->d_tri;
+        a->mroot = sc->n_faces ? sc->mbvh.root_ref : kNoRoot;
+        a->n_faces = sc->n_faces;
+        a->faces = sc->d_faces;
+        a->vnormals = sc->d_vnormals;
+    }
     a->swizzle_chunk = (uint32_t)c->opt_swizzle;
     a->err_word = c->d_err;
     return GRT_OK;
 }
-#endif // !GRT_BWD_MESH_TU
 
-#ifdef GRT_BWD_MAIN_TU
+int bwd_set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const char* fn)
+{
+    if (x1 > p->width || y1 > p->height || x0 > x1 || y0 > y1) { c->err = std::string(fn) + ": window outside the frame"; return GRT_ERR_INVALID; }
+    a->mode = 0;
+    a->x0 = x0; a->y0 = y0; a->x1 = x1; a->y1 = y1;
+    a->nbx = (x1 - x0 + 15) / 16;
+    a->nby = (y1 - y0 + 15) / 16;
+    a->n_blocks = a->nbx * a->nby;
+    return GRT_OK;
+}
+
+int bwd_set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const char* fn)
+{
+    if (n && !d_rays) { c->err = std::string(fn) + ": null ray buffer"; return GRT_ERR_INVALID; }
+    if (n > 0xFFFFFFFFull * 64) { c->err = std::string(fn) + ": too many rays"; return GRT_ERR_LIMIT; }
+    a->mode = 2;
+    a->rays = d_rays; a->n_rays = n;
+    a->n_blocks = (uint32_t)((n + 255) / 256);
+    return GRT_OK;
+}
+
+int bwd_launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha,
+               const grt_gaussian_grads* g, float* d_ray_grads, const void* const kernels[3], void* stream, const char* fn)
+{
+    const grt_ctx* sc = c->parent ? c->parent : c;
+    const uint64_t n = sc->n;
+    const bool want_geom = g && (g->pos || g->scale || g->quat || g->opacity);
+    const bool want_sh = g && g->sh;
+    const bool gauss = (want_geom || want_sh) && n != 0 && sc->gbvh.root_ref != kNoRoot;
+    // no ray, or nothing to differentiate (with a per-ray output an empty scene or an empty tree still runs: the rays-only kernel writes the zeros)
+    if (a.n_blocks == 0 || (!gauss && !d_ray_grads)) { c->have_timing = false; return GRT_OK; }
+    CHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const bool hi = gauss && p->sh_degree_max > 0 && want_sh;
+    if (gauss) {
+        int rc = bwd_buffers(c, n, hi, s);
+        if (rc != GRT_OK) return rc;
+    }
+    // one LDS stack per lane, for the Gaussian tree and, in a frame with meshes, for the mesh tree in turn
+    const uint32_t depth = std::max(std::max(sc->gbvh.height, a.n_faces ? sc->mbvh.height : 0u), 1u);
+    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
+    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
+    BwdArgs b;
+    b.pos = sc->d_pos; b.scale = sc->d_scale; b.quat = sc->d_quat; b.opacity = sc->d_opacity;
+    b.g_rgb = d_grad_rgbf; b.g_alpha = d_grad_alpha;
+    b.acc = gauss ? c->d_gacc : nullptr; b.acc_sh = hi ? c->d_gacc_sh : nullptr;
+    b.want_geom = (want_geom || d_ray_grads) ? 1u : 0u; // (the rays need m = A^T g_p of every event)
+    b.want_sh = (gauss && want_sh) ? 1u : 0u;
+    RayOut ro;
+    ro.rays = d_ray_grads;
+    ro.scatter_geom = (gauss && want_geom) ? 1u : 0u;
+    const void* fnk = kernels[!gauss ? 0 : (c->opt_bwd_plain ? 1 : 2)];
+    CHK(c, hipFuncSetAttribute(fnk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CHK(c, hipEventRecord(c->ev0, s));
+    void* args[3] = {const_cast<RenderArgs*>(&a), &b, &ro}; // (a kernel without a per-ray output takes the first two)
+    (void)hipLaunchKernel(fnk, dim3(a.n_blocks), dim3(kBlock), args, lds, s); // (a failed launch: hipGetLastError below / in bwd_flush)
+    if (gauss) return bwd_flush(c, n, hi, g, s);
+    CHK(c, hipGetLastError());
+    CHK(c, hipEventRecord(c->ev1, s));
+    c->have_timing = true;
+    return GRT_OK;
+}
+
+} // namespace grt
+
+static int launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf,
+                  const float* d_grad_alpha, const grt_gaussian_grads* g, void* stream, const char* fn)
+{
+    if (!d_rgbf || !d_alpha || !d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_rgbf, d_alpha, d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
+    static const void* const kernels[3] = {nullptr, reinterpret_cast<const void*>(k_backward<false>), reinterpret_cast<const void*>(k_backward<true>)};
+    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, nullptr, kernels, stream, fn);
+}
+
 extern "C" {
 
 int grt_backward(grt_ctx* c, const grt_params* p, const float* d_rgbf, const float* d_alpha, const float* d_grad_rgbf, const float* d_grad_alpha,
                  const grt_gaussian_grads* g, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream)
 {
+    const char* fn = "grt_backward";
     RenderArgs a;
-    int rc = backward_common(c, p, &a, "grt_backward");
+    int rc = bwd_fill_args(c, p, false, &a, fn);
+    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
     if (rc != GRT_OK) return rc;
-    if (x1 > p->width || y1 > p->height || x0 > x1 || y0 > y1) { c->err = "grt_backward: window outside the frame"; return GRT_ERR_INVALID; }
-    a.mode = 0;
-    a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
-    a.nbx = (x1 - x0 + 15) / 16;
-    a.nby = (y1 - y0 + 15) / 16;
-    a.n_blocks = a.nbx * a.nby;
-    return backward_launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, g, stream, "grt_backward");
+    return launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, g, stream, fn);
 }
 
 int grt_backward_rays(grt_ctx* c, const grt_params* p, const float* d_rays, uint64_t n, const float* d_rgbf, const float* d_alpha,
                       const float* d_grad_rgbf, const float* d_grad_alpha, const grt_gaussian_grads* g, void* stream)
 {
+    const char* fn = "grt_backward_rays";
     RenderArgs a;
-    int rc = backward_common(c, p, &a, "grt_backward_rays");
+    int rc = bwd_fill_args(c, p, false, &a, fn);
+    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
     if (rc != GRT_OK) return rc;
-    if (n && !d_rays) { c->err = "grt_backward_rays: null ray buffer"; return GRT_ERR_INVALID; }
-    if (n > 0xFFFFFFFFull * 64) { c->err = "grt_backward_rays: too many rays"; return GRT_ERR_LIMIT; }
-    a.mode = 2;
-    a.rays = d_rays; a.n_rays = n;
-    a.n_blocks = (uint32_t)((n + 255) / 256);
     if (n == 0) { // (no ray: nothing to read either)
         if (!g) { c->err = "grt_backward_rays: null grads structure"; return GRT_ERR_INVALID; }
         c->have_timing = false;
         return GRT_OK;
     }
-    return backward_launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, g, stream, "grt_backward_rays");
+    return launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, g, stream, fn);
 }
 
 } // extern "C"
-#endif

@@ -2,8 +2,7 @@
 // 5.11): gradients of a loss on (rgbf, alpha) of a frame whose rays bounce off mirror, glass or normal-shaded meshes, with respect
 // to the activated attributes of the Gaussians.  Meshes and every discrete decision are held fixed.
 //
-// A translation unit of its own.  It includes grt_backward.hip under GRT_BWD_MESH_TU (the technique of grt_backward_rays.hip):
-// event_terms, scatter and what they use are that file's ONE text; its kernels, flush kernels and entry points are compiled away.
+// k_backward_mesh<MERGE>, on the shared device text of grt_bwd.h: a lane's ray and upstream gradient, event_terms and scatter.
 //
 // One ray per lane.  The two sweeps of k_backward, each wrapped in the raygen bounce loop (grt_render.hip: shade_ray):
 //   sweep 0  runs the whole loop — mesh hit, next ray, the iteration's Gaussian segment with the transmittance carried on — and
@@ -27,9 +26,9 @@
 // `it` / `act` cleared.  The mesh walk is the per-lane mesh_closest_t and the k-nearest round the per-lane gps_round, both inside
 // `if (it)` / `if (act)` and neither with a wave operation in it.  A lane's iterations are bounded by max_bounces and the
 // 1000-iteration timeout, its rounds by lastT rising past the segment's end: every ballot becomes zero.
-#define GRT_BWD_MESH_TU 1
-#include "grt_backward.hip"
+#include <string>
 
+#include "grt_bwd.h"
 #include "grt_mesh.h"
 
 namespace grt {
@@ -52,42 +51,14 @@ __global__ __launch_bounds__(kBlock) void k_backward_mesh(const RenderArgs a, co
     constexpr bool GAUSS = true, RAYS = false;
     extern __shared__ uint32_t lds_stack[];
     uint32_t* stk = lds_stack + threadIdx.x;
-    const uint32_t blk = xcd_swizzle(blockIdx.x, a.n_blocks, a.swizzle_chunk);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t lx = (wave & 1u) * 8u + (lane & 7u), ly = (wave >> 1) * 8u + (lane >> 3);
-    size_t idx = 0;
-    bool live = false;
-    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
-    if (a.mode == 2) { // ray buffer
-        const uint64_t i = (uint64_t)blk * kBlock + threadIdx.x;
-        if (i < a.n_rays) {
-            const float* r = a.rays + i * 6;
-            o = mk3(r[0], r[1], r[2]);
-            d = mk3(r[3], r[4], r[5]);
-            idx = (size_t)i;
-            live = true;
-        }
-    } else { // window of the full frame
-        const uint32_t px = a.x0 + (blk % a.nbx) * 16u + lx;
-        const uint32_t py = a.y0 + (blk / a.nbx) * 16u + ly;
-        idx = (size_t)py * a.p.width + px;
-        if ((px < a.x1) && (py < a.y1)) {
-            const f3 nU = mk3(-a.p.U[0], -a.p.U[1], -a.p.U[2]), nV = mk3(-a.p.V[0], -a.p.V[1], -a.p.V[2]);
-            const f3 W = mk3(a.p.W[0], a.p.W[1], a.p.W[2]);
-            live = true;
-            if (!a.p.mode_fisheye) get_ray(px, py, nU, nV, W, a.p.width, a.p.height, d);
-            else live = get_fisheye_ray(px, py, nU, nV, W, a.p.width, a.p.height, d);
-            o = mk3(a.p.eye[0], a.p.eye[1], a.p.eye[2]);
-        }
-    }
-    live = live && (a.root_ref != kNoRoot);
-    f3 gC = mk3(0, 0, 0);
-    float gA = 0.0f;
-    if (live) {
-        gC = mk3(b.g_rgb[idx * 3], b.g_rgb[idx * 3 + 1], b.g_rgb[idx * 3 + 2]);
-        if (b.g_alpha) gA = b.g_alpha[idx];
-        live = (gC.x != 0.0f) || (gC.y != 0.0f) || (gC.z != 0.0f) || (gA != 0.0f); // zero upstream: nothing is added
-    }
+    uint32_t lane;
+    size_t idx;
+    bool has_out; // (unused: nothing is written per ray)
+    f3 o, d;
+    bool live = lane_ray(a, lane, o, d, idx, has_out) && (a.root_ref != kNoRoot);
+    f3 gC;
+    float gA;
+    live = load_upstream(b, idx, live, gC, gA);
     if (!__builtin_amdgcn_ballot_w64(live)) return; // wave-uniform
 
     const float epsT = 1e-9f;
@@ -230,65 +201,14 @@ __global__ __launch_bounds__(kBlock) void k_backward_mesh(const RenderArgs a, co
 } // namespace
 } // namespace grt
 
-static int backward_mesh_common(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
-{
-    if (!c) return GRT_ERR_INVALID;
-    if (!p) { c->err = std::string(fn) + ": null parameters"; return GRT_ERR_INVALID; }
-    const grt_ctx* sc = c->parent ? c->parent : c;
-    if (!sc->built) { c->err = std::string(fn) + ": grt_build_bvh has not been called after the last upload"; return GRT_ERR_INVALID; }
-    if (c->opt_counters) { c->err = std::string(fn) + ": GRT_OPT_COUNTERS = 1 (the backward kernel is not instrumented)"; return GRT_ERR_INVALID; }
-    if (p->sh_degree_max > 3) { c->err = std::string(fn) + ": sh_degree_max must be 0..3"; return GRT_ERR_INVALID; }
-    if (p->type < 0 || p->type > 2) { c->err = std::string(fn) + ": type must be MIRROR/NORMAL/GLASS"; return GRT_ERR_INVALID; }
-    if (!(p->t_min > 0.0f)) { c->err = std::string(fn) + ": t_min must be > 0"; return GRT_ERR_INVALID; }
-    memset(a, 0, sizeof(*a));
-    a->p = *p;
-    a->rec = sc->d_rec;
-    a->nodes = sc->gbvh.nodes;
-    a->root_ref = sc->gbvh.root_ref;
-    a->n_prox = sc->gbvh.n_prims;
-    a->has_pieces = sc->has_pieces ? 1u : 0u;
-    a->color0 = sc->d_color0;
-    a->sh = sc->d_sh;
-    // the mesh side, as the per-lane aux launch has it (grt_api.hip: fill_common)
-    a->mnodes = sc->mbvh.nodes;
-    a->tri = sc->d_tri;
-    a->mroot = sc->n_faces ? sc->mbvh.root_ref : kNoRoot;
-    a->n_faces = sc->n_faces;
-    a->faces = sc->d_faces;
-    a->vnormals = sc->d_vnormals;
-    a->swizzle_chunk = (uint32_t)c->opt_swizzle;
-    a->err_word = c->d_err;
-    return GRT_OK;
-}
+using namespace grt;
 
-// a: mode, window / rays and n_blocks set by the caller
-static int backward_mesh_launch(grt_ctx* c, const grt_params* p, RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha,
-                                const grt_gaussian_grads* g, void* stream, const char* fn)
+static int launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha, const grt_gaussian_grads* g,
+                  void* stream, const char* fn)
 {
-    const grt_ctx* sc = c->parent ? c->parent : c;
     if (!d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
-    const uint64_t n = sc->n;
-    const bool want_geom = g->pos || g->scale || g->quat || g->opacity;
-    if (a.n_blocks == 0 || n == 0 || sc->gbvh.root_ref == kNoRoot || (!want_geom && !g->sh)) { c->have_timing = false; return GRT_OK; } // nothing to differentiate
-    CHK(c, hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const bool hi = p->sh_degree_max > 0 && g->sh;
-    int rc = bwd_buffers(c, n, hi, s);
-    if (rc != GRT_OK) return rc;
-    // one LDS stack per lane, for the Gaussian tree and for the mesh tree in turn
-    const uint32_t depth = std::max(std::max(sc->gbvh.height, sc->n_faces ? sc->mbvh.height : 0u), 1u);
-    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
-    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
-    BwdArgs b;
-    b.pos = sc->d_pos; b.scale = sc->d_scale; b.quat = sc->d_quat; b.opacity = sc->d_opacity;
-    b.g_rgb = d_grad_rgbf; b.g_alpha = d_grad_alpha;
-    b.acc = c->d_gacc; b.acc_sh = hi ? c->d_gacc_sh : nullptr;
-    b.want_geom = want_geom ? 1u : 0u; b.want_sh = g->sh ? 1u : 0u;
-    auto fnk = c->opt_bwd_plain ? k_backward_mesh<false> : k_backward_mesh<true>;
-    CHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(fnk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CHK(c, hipEventRecord(c->ev0, s));
-    hipLaunchKernelGGL(fnk, dim3(a.n_blocks), dim3(kBlock), lds, s, a, b);
-    return bwd_flush(c, n, hi, g, s);
+    static const void* const kernels[3] = {nullptr, reinterpret_cast<const void*>(k_backward_mesh<false>), reinterpret_cast<const void*>(k_backward_mesh<true>)};
+    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, nullptr, kernels, stream, fn);
 }
 
 extern "C" {
@@ -296,35 +216,28 @@ extern "C" {
 int grt_backward_mesh(grt_ctx* c, const grt_params* p, const float* d_grad_rgbf, const float* d_grad_alpha, const grt_gaussian_grads* g,
                       uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream)
 {
+    const char* fn = "grt_backward_mesh";
     RenderArgs a;
-    int rc = backward_mesh_common(c, p, &a, "grt_backward_mesh");
+    int rc = bwd_fill_args(c, p, true, &a, fn);
+    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
     if (rc != GRT_OK) return rc;
-    if (x1 > p->width || y1 > p->height || x0 > x1 || y0 > y1) { c->err = "grt_backward_mesh: window outside the frame"; return GRT_ERR_INVALID; }
-    a.mode = 0;
-    a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
-    a.nbx = (x1 - x0 + 15) / 16;
-    a.nby = (y1 - y0 + 15) / 16;
-    a.n_blocks = a.nbx * a.nby;
-    return backward_mesh_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, stream, "grt_backward_mesh");
+    return launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, stream, fn);
 }
 
 int grt_backward_rays_mesh(grt_ctx* c, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_rgbf,
                            const float* d_grad_alpha, const grt_gaussian_grads* g, void* stream)
 {
+    const char* fn = "grt_backward_rays_mesh";
     RenderArgs a;
-    int rc = backward_mesh_common(c, p, &a, "grt_backward_rays_mesh");
+    int rc = bwd_fill_args(c, p, true, &a, fn);
+    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
     if (rc != GRT_OK) return rc;
-    if (n && !d_rays) { c->err = "grt_backward_rays_mesh: null ray buffer"; return GRT_ERR_INVALID; }
-    if (n > 0xFFFFFFFFull * 64) { c->err = "grt_backward_rays_mesh: too many rays"; return GRT_ERR_LIMIT; }
-    a.mode = 2;
-    a.rays = d_rays; a.n_rays = n;
-    a.n_blocks = (uint32_t)((n + 255) / 256);
     if (n == 0) { // (no ray: nothing to read either)
         if (!g) { c->err = "grt_backward_rays_mesh: null grads structure"; return GRT_ERR_INVALID; }
         c->have_timing = false;
         return GRT_OK;
     }
-    return backward_mesh_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, stream, "grt_backward_rays_mesh");
+    return launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, stream, fn);
 }
 
 } // extern "C"

@@ -447,8 +447,17 @@ struct grt_ctx {
 };
 
 namespace grt {
-// grt_backward.hip, shared with grt_backward_rays.hip: the context's gradient buffers made ready for a backward kernel on s, and the
-// flush kernels behind it (with the events that end a backward call).  GRT_OK or GRT_ERR_HIP (text in c->err).
-int bwd_buffers(grt_ctx* c, uint64_t n, bool hi, hipStream_t s);
-int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* g, hipStream_t s);
+// grt_backward.hip: the host path of the backward entry points (grt_backward*.hip).  Each returns GRT_OK or the refusal's code, its
+// text in c->err with the entry point's name `fn` in front.
+// The arguments every backward kernel reads, after the refusals all entry points share (null p, no BVH, counters on, sh_degree_max,
+// t_min).  mesh: the mesh side is filled and p->type checked; without it a scene with meshes is refused.
+int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn);
+// The work mapping: a window of the frame (refused when outside it), or a ray buffer (refused when null, or too long).
+int bwd_set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const char* fn);
+int bwd_set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const char* fn);
+// The launch: gradient buffers, LDS stack, the kernel between ev0 and ev1, the flush.  kernels: the calling unit's instantiations —
+// [0] the one that scatters nothing (runs when there is a per-ray output d_ray_grads and no Gaussian gradient to form; else null),
+// [1] plain atomics, [2] the wave merge — each taking (RenderArgs, BwdArgs) or (RenderArgs, BwdArgs, RayOut) of grt_bwd.h.
+int bwd_launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha,
+               const grt_gaussian_grads* g, float* d_ray_grads, const void* const kernels[3], void* stream, const char* fn);
 }  // namespace grt

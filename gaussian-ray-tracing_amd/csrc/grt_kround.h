@@ -1,7 +1,8 @@
 // grt_kround.h — the per-lane k-nearest round: the k-buffer, its insert, one BVH round and the radiance of an event.
 //
-// ONE text for the forward per-lane kernels (grt_render.hip) and the backward pass (grt_backward.hip): the backward is right only
-// while it builds the same k-buffer in the same order as the forward, and here that is a fact of the include.
+// ONE text for the forward per-lane kernels (grt_render.hip) and the backward pass (grt_bwd.h, the header of the three backward
+// units, and grt_backward_mesh.hip): the backward is right only while it builds the same k-buffer in the same order as the
+// forward, and here that is a fact of the include.
 // (The wave kernel, grt_render_wave.hip with its branch-free kbuf_insert and gps_round_wave, the stream body and the tile kernel
 //  stay independent on purpose: "four independent traversals, bit for bit" is a test asset.)
 #pragma once
