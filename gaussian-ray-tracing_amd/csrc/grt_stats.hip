@@ -1,0 +1,225 @@
+// grt_stats.hip — per-particle contribution statistics of a Gaussian-only frame (include/grt.h: grt_particle_stats_frame /
+// grt_particle_stats_rays): for every particle the sum and the peak of its compositing weights T_i alpha_i and the
+// number of its composited events, over the rays of a window or of a ray buffer.
+//
+// k_particle_stats<MERGE> is ONE sweep of the backward's body (grt_bwd.h: backward_body) without colour: lane_ray gives the ray, one
+// ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round (grt_kround.h) through a single call site, every lane of the wave in
+// step.  Per slot of the k-buffers the wave scatters as scatter<MERGE> does: the lanes that hold the same particle form a group
+// (ballot / readlane); the group's count is the popcount of its ballot, its sum wave_sum, its peak the same ladder with fmaxf, and
+// its leader issues one atomic per requested output; a lane alone with its particle issues its own.  MERGE = false
+// (GRT_OPT_BWD_PLAIN_ATOMICS = 1): every lane issues its own.  The atomics go straight into the caller's arrays: float add,
+// unsigned max on the bit pattern of a non-negative float, unsigned add.  The context owns no buffer for this.
+#include <algorithm>
+#include <string>
+
+#include "grt_bwd.h"
+
+namespace grt {
+namespace {
+
+static_assert(kBlock == kRoundBlock, "k_particle_stats runs gps_round (grt_kround.h): its per-lane stack stride is the launch block size");
+
+struct StatsArgs {
+    const float* ray_weight; // [pixels or rays] or null (= 1)
+    float* weight_sum;       // [n] by original id, or null
+    float* weight_max;       // [n] or null
+    uint32_t* count;         // [n] or null
+};
+
+// max over the wave of v >= 0 (lanes outside the group hold 0), as a wave-uniform value: wave_sum's ladder (grt_bwd.h) with fmaxf
+__device__ __forceinline__ float wave_max(float v)
+{
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));  // quad_perm [1,0,3,2]
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));  // quad_perm [2,3,0,1]
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true))); // row_half_mirror
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true))); // row_mirror
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+
+// one atomic per requested output (the branches are wave-uniform: kernel arguments)
+__device__ __forceinline__ void stats_add(const StatsArgs& s, uint32_t id, float sum, float peak, uint32_t n)
+{
+    if (s.weight_sum) atomicAdd(s.weight_sum + id, sum);
+    if (s.weight_max) atomicMax(reinterpret_cast<unsigned int*>(s.weight_max) + id, __float_as_uint(peak)); // (peak >= 0: its bits order as it does)
+    if (s.count) atomicAdd(s.count + id, n);
+}
+
+// Called by the WHOLE wave (ev: this lane has an event of particle id with weight w = T alpha; ws = w_ray * w).
+template <bool MERGE>
+__device__ __forceinline__ void stats_scatter(const StatsArgs& s, bool ev, uint32_t id, float ws, float w, uint32_t lane)
+{
+    if (!MERGE) {
+        if (ev) stats_add(s, id, ws, w, 1u);
+        return;
+    }
+    uint64_t todo = __builtin_amdgcn_ballot_w64(ev);
+    bool solo = false;
+    while (todo) { // wave-uniform
+        const int leader = __builtin_ctzll(todo);
+        const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, leader);
+        const bool mine = ev && id == lid;
+        const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
+        todo &= ~m;
+        const uint32_t n = (uint32_t)__builtin_popcountll(m);
+        if (n == 1u) { // alone with its particle: its own atomics, once the groups are done
+            solo = solo || mine;
+            continue;
+        }
+        float sum = 0.0f, peak = 0.0f;
+        if (s.weight_sum) sum = wave_sum(mine ? ws : 0.0f);
+        if (s.weight_max) peak = wave_max(mine ? w : 0.0f);
+        if (lane == (uint32_t)leader) stats_add(s, lid, sum, peak, n);
+    }
+    if (solo) stats_add(s, id, ws, w, 1u);
+}
+
+template <bool MERGE>
+__global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, const StatsArgs s)
+{
+    extern __shared__ uint32_t lds_stack[];
+    uint32_t* stk = lds_stack + threadIdx.x;
+    uint32_t lane;
+    size_t idx;
+    bool has_out;
+    f3 o, d;
+    bool live = lane_ray(a, lane, o, d, idx, has_out);
+    // the raygen loop's guard, as the backward has it (shaders/tracer.cu:59)
+    live = live && (length3(d) > 0.1f) && (a.p.max_bounces > 0u) && (a.root_ref != kNoRoot);
+    float wr = 1.0f;
+    if (live && s.ray_weight) {
+        wr = s.ray_weight[idx];
+        live = wr != 0.0f; // a ray of weight exactly 0 is not traced
+    }
+    if (!__builtin_amdgcn_ballot_w64(live)) return; // wave-uniform
+
+    const rayinv ri = mk_rayinv(o, d);
+    const float epsT = 1e-9f;
+    const float t_max = a.p.t_max;
+    const float t_hi = t_max + epsT;
+    const float minT = a.p.minTransmittance;
+    KBuf<K> kb;
+    Cnt cnt; // (dead: no counters, no watchdog)
+
+    // one sweep over the events trace() composites (shaders/tracer.cuh:328-373), every lane of the wave in step: the scatter is
+    // wave-cooperative, a finished lane idles
+    float T = 1.0f, lastT = a.p.t_min;
+    uint64_t last_key = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
+    bool act = live && (lastT <= t_max) && (T > minT);
+    while (__builtin_amdgcn_ballot_w64(act)) {
+        if (act) {
+            gps_round<false, false, K>(a, stk, o, d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
+            if (kb.key[0] == kKeyInvalid) act = false;
+        }
+#pragma unroll 1
+        for (int i = 0; i < K; i++) {
+            bool ev = false;
+            uint32_t id = 0;
+            float w = 0.0f;
+            uint64_t key = kKeyInvalid;
+            float hitAlpha = 0.0f;
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                if (j == i) { key = kb.key[j]; hitAlpha = kb.alpha[j]; }
+            }
+            if (act && key != kKeyInvalid && T > minT) {
+                lastT = fmaxf(key_t(key), lastT);
+                if (a.p.alpha_min < hitAlpha) {
+                    ev = true;
+                    id = key_id(key);
+                    w = T * hitAlpha; // T: the transmittance before the event
+                    T *= (1.0f - hitAlpha);
+                }
+            }
+            stats_scatter<MERGE>(s, ev, id, wr * w, w, lane);
+        }
+        if (act) {
+            if (kb.key[K - 1] == kKeyInvalid) act = false;
+            else last_key = kb.key[K - 1];
+            act = act && (lastT <= t_max) && (T > minT);
+        }
+    }
+}
+
+} // namespace
+} // namespace grt
+
+using namespace grt;
+
+#define CHK(ctx, x)                                                                                   \
+    do {                                                                                              \
+        hipError_t e_ = (x);                                                                          \
+        if (e_ != hipSuccess) {                                                                       \
+            (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"; \
+            return GRT_ERR_HIP;                                                                       \
+        }                                                                                             \
+    } while (0)
+
+// what both entry points refuse before they look at their rays: the backward's refusals in the entry point's name, and a scene with meshes
+static int fill(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
+{
+    if (!c) return GRT_ERR_INVALID;
+    const grt_ctx* sc = c->parent ? c->parent : c;
+    if (p && sc->built && sc->n_faces) {
+        c->err = std::string(fn) + ": meshes are set (particle statistics are computed for Gaussian-only frames)";
+        return GRT_ERR_INVALID;
+    }
+    return bwd_fill_args(c, p, false, a, fn);
+}
+
+static int launch(grt_ctx* c, const RenderArgs& a, const float* d_ray_weight, const grt_particle_stats* out, void* stream, const char* fn)
+{
+    if (!out || (!out->weight_sum && !out->weight_max && !out->count)) {
+        c->err = std::string(fn) + ": no output (weight_sum, weight_max and count are all NULL)";
+        return GRT_ERR_INVALID;
+    }
+    const grt_ctx* sc = c->parent ? c->parent : c;
+    // no ray, no particle or an empty tree: nothing is composited, nothing is written
+    if (a.n_blocks == 0 || sc->n == 0 || sc->gbvh.root_ref == kNoRoot) { c->have_timing = false; return GRT_OK; }
+    CHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const uint32_t depth = std::max(sc->gbvh.height, 1u);
+    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth; // one LDS stack per lane
+    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
+    StatsArgs sa;
+    sa.ray_weight = d_ray_weight;
+    sa.weight_sum = out->weight_sum; sa.weight_max = out->weight_max; sa.count = out->count;
+    const void* fnk = c->opt_bwd_plain ? reinterpret_cast<const void*>(k_particle_stats<false>) : reinterpret_cast<const void*>(k_particle_stats<true>);
+    CHK(c, hipFuncSetAttribute(fnk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CHK(c, hipEventRecord(c->ev0, s));
+    void* args[2] = {const_cast<RenderArgs*>(&a), &sa};
+    (void)hipLaunchKernel(fnk, dim3(a.n_blocks), dim3(kBlock), args, lds, s);
+    CHK(c, hipGetLastError());
+    CHK(c, hipEventRecord(c->ev1, s));
+    c->have_timing = true;
+    return GRT_OK;
+}
+
+extern "C" {
+
+int grt_particle_stats_frame(grt_ctx* c, const grt_params* p, const float* d_ray_weight, const grt_particle_stats* out, uint32_t x0, uint32_t y0,
+                             uint32_t x1, uint32_t y1, void* stream)
+{
+    const char* fn = "grt_particle_stats_frame";
+    RenderArgs a;
+    int rc = fill(c, p, &a, fn);
+    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
+    if (rc != GRT_OK) return rc;
+    return launch(c, a, d_ray_weight, out, stream, fn);
+}
+
+int grt_particle_stats_rays(grt_ctx* c, const grt_params* p, const float* d_rays, uint64_t n, const float* d_ray_weight, const grt_particle_stats* out,
+                            void* stream)
+{
+    const char* fn = "grt_particle_stats_rays";
+    RenderArgs a;
+    int rc = fill(c, p, &a, fn);
+    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
+    if (rc != GRT_OK) return rc;
+    return launch(c, a, d_ray_weight, out, stream, fn);
+}
+
+} // extern "C"

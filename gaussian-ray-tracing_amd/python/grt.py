@@ -71,6 +71,11 @@ class BackwardOut(C.Structure):
     _fields_ = [("gaussians", C.POINTER(GaussianGrads)), ("rays", C.c_void_p)]
 
 
+class ParticleStats(C.Structure):
+    """grt_particle_stats (include/grt.h): device pointers of the per-particle weight_sum / weight_max / count arrays, each may be NULL."""
+    _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("count", C.c_void_p)]
+
+
 class UpdateInfo(C.Structure):
     """grt_update_info (include/grt.h): what grt_update_gaussians_device did."""
     _fields_ = [("mode_used", C.c_uint32), ("reason", C.c_uint32), ("device_ms", C.c_float), ("area_ratio", C.c_float)]
@@ -81,6 +86,7 @@ UPDATE_MODES = {"auto": UPDATE_AUTO, "refit": UPDATE_REFIT, "rebuild": UPDATE_RE
 REASON_NONE, REASON_FIRST_BUILD, REASON_N_CHANGED, REASON_SET_CHANGED, REASON_OPTION_CHANGED, REASON_AREA = 0, 1, 2, 3, 4, 5
 
 GRAD_SHAPES = {"pos": (3,), "scale": (3,), "quat": (4,), "opacity": (), "sh": (16, 3)}
+STATS_OUTPUTS = ("weight_sum", "weight_max", "count")
 
 
 class Mesh(C.Structure):
@@ -113,7 +119,8 @@ EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
     "grt_update_gaussians_device",
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
-    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh", "grt_sync",
+    "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
+    "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -166,6 +173,8 @@ def lib():
         L.grt_backward_rays_ex.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, vp, vp, C.POINTER(BackwardOut), vp]
         L.grt_backward_mesh.argtypes = [vp, C.POINTER(Params), vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
         L.grt_backward_rays_mesh.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, C.POINTER(GaussianGrads), vp]
+        L.grt_particle_stats_frame.argtypes = [vp, C.POINTER(Params), vp, C.POINTER(ParticleStats), u32, u32, u32, u32, vp]
+        L.grt_particle_stats_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(ParticleStats), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -606,6 +615,53 @@ class Tracer:
         into, ptrs = self._grad_buffers(into, groups, rays.device)
         self._check(lib().grt_backward_rays_mesh(self._h, C.byref(params), rays.data_ptr(), rays.shape[0],
                                                  *(x.data_ptr() if x is not None else None for x in keep), C.byref(ptrs), self._stream()))
+        return into
+
+    def particle_stats(self, params, rays=None, ray_weight=None, window=None, into=None, outputs=STATS_OUTPUTS):
+        """grt_particle_stats_frame / grt_particle_stats_rays (rays [n][6] given): which particles the rays of the frame (or of its
+        window, or of the buffer) composited, and how strongly -> dict of torch tensors [n_particles] by original id on the tracer's
+        GPU: 'weight_sum' float32 (sum of ray_weight * T_i * alpha_i over the composited events), 'weight_max' float32 (peak
+        T_i * alpha_i, not scaled by the ray's weight), 'count' uint32 as render_aux's (number of composited events); include/grt.h.
+        ray_weight: [h][w] or [n] float32 (None = 1); a ray of weight exactly 0 is not traced and enters none of the three.
+        The tensors are allocated zeroed for `outputs`, or the call ACCUMULATES (add, max, add) into the tensors of `into` (its keys
+        are the outputs computed; 'count' may be uint32 or int32): several views sum up into one dict.  count and weight_max are
+        bitwise reproducible, weight_sum is not (float atomics)."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if into is None:
+            bad = [k for k in outputs if k not in STATS_OUTPUTS]
+            if bad or not len(outputs):
+                raise GrtError(f"particle_stats: outputs must be a non-empty subset of {STATS_OUTPUTS}, not {tuple(outputs)}")
+            into = {k: t.zeros((n,), dtype=t.uint32 if k == "count" else t.float32, device=dev) for k in outputs}
+        for k, v in into.items():
+            ok_dt = (t.uint32, t.int32) if k == "count" else (t.float32,)
+            if k not in STATS_OUTPUTS or tuple(v.shape) != (n,) or v.dtype not in ok_dt or not v.is_contiguous() or v.device != dev:
+                raise GrtError(f"particle_stats: tensor '{k}' must be contiguous {'uint32 / int32' if k == 'count' else 'float32'} of shape "
+                               f"({n},) on {dev}")
+        ptrs = ParticleStats(*(into[k].data_ptr() if k in into and n else None for k in STATS_OUTPUTS))
+        if not n:  # (an empty scene: nothing to write, and no pointer to hand over)
+            return into
+        if rays is not None:
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"particle_stats: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        if ray_weight is not None:
+            ray_weight = t.as_tensor(ray_weight).detach().to(dev, t.float32).contiguous()
+            if tuple(ray_weight.shape) != shape:
+                raise GrtError(f"particle_stats: ray_weight must have shape {shape}, not {tuple(ray_weight.shape)}")
+        wp = ray_weight.data_ptr() if ray_weight is not None else None
+        if rays is not None:
+            if window is not None:
+                raise GrtError("particle_stats: rays and window exclude each other")
+            self._check(lib().grt_particle_stats_rays(self._h, C.byref(params), rays.data_ptr() if shape[0] else None, shape[0], wp,
+                                                      C.byref(ptrs), self._stream()))
+        else:
+            x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
+            self._check(lib().grt_particle_stats_frame(self._h, C.byref(params), wp, C.byref(ptrs), x0, y0, x1, y1, self._stream()))
         return into
 
     def _ex_buffers(self, into, groups, dev, ray_shape):

@@ -134,3 +134,15 @@ def render(tracer, params, pos, scale, quat, opacity, sh, rays=None, update="aut
         if any(t.requires_grad for t in camera):
             cam_rays, _ = camera_rays(eye, U, V, W, params.width, params.height, bool(params.mode_fisheye))
     return _Render.apply(pos, scale, quat, opacity, sh, rays, cam_rays, tracer, params, update)
+
+
+def particle_stats(tracer, params, rays=None, ray_weight=None, into=None):
+    """Per-particle contribution statistics of the frame (or of `rays` [n][6]) under torch.no_grad(): a dict of 'weight_sum',
+    'weight_max' (float32) and 'count' tensors [n_particles] on the tracer's GPU (Tracer.particle_stats; include/grt.h:
+    grt_particle_stats_frame / grt_particle_stats_rays) — which particles the view composited and how strongly, for visibility
+    masks, densification gates and pruning.  Like the backward it reads the scene the tracer HOLDS: call it right after
+    grt_torch.render(tracer, ...), before the next upload to the same tracer.  ray_weight ([h][w] or [n]; None = 1) scales
+    weight_sum, and a ray of weight exactly 0 is not traced; `into` accumulates several views into one dict.  Nothing here is
+    differentiable: the tensors carry no graph."""
+    with torch.no_grad():
+        return tracer.particle_stats(params, rays=rays, ray_weight=ray_weight, into=into)

@@ -507,6 +507,46 @@ GRT_API int grt_backward_mesh(grt_ctx* ctx, const grt_params* p, const float* d_
                               const grt_gaussian_grads* grads, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_backward_rays_mesh(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_rgbf,
                                    const float* d_grad_alpha, const grt_gaussian_grads* grads, void* stream);
+/* ---- per-particle contribution statistics: which particles a set of rays touched, and how strongly (Gaussian-only frames) ----
+ * What visibility masks, densification gates ("was seen") and pruning ("never seen", "never significant") read beside the gradients.
+ * The compositing weights exist only inside the traversal, so the answer comes from a traversal of its own.  A COMPOSITED EVENT is
+ * exactly the backward pass's (above): the k-buffer's events i in key order (t, id, entry < exit), BOTH the entry and the exit event
+ * of a proxy, repeats of a split particle's pieces dropped, an event counted when alpha_min < alpha_i, the walk going on while
+ * T > minTransmittance and the last distance <= t_max.  Its weight is
+ *     w_i = T_i alpha_i,     T_1 = 1, T_{i+1} = T_i (1 - alpha_i)       (T_i: the transmittance BEFORE the event)
+ * both factors float32 and formed with the forward's own arithmetic, the product one float32 multiplication.  Over the rays r of the
+ * window (grt_particle_stats_frame) or of the buffer (grt_particle_stats_rays), for every particle j by ORIGINAL id:
+ *     weight_sum[j] += sum over the composited events of j on r of  w_ray(r) * w_i
+ *     weight_max[j]  = max(weight_max[j], max over those events of  w_i)                (NOT scaled by w_ray)
+ *     count[j]      += the number of those events
+ * (with unit ray weights the sum of weight_sum over all particles is the sum over the rays of 1 - T_end: grt_aux_out::alpha before
+ * its clamp; the sum of count is the sum of grt_aux_out::count.)
+ *   d_ray_weight   [h][w] (laid out like the frame, read inside the window) or [n]; NULL = 1 for every ray.  A ray whose weight is
+ *                  EXACTLY 0 is not traced and contributes to none of the three outputs (a mask: weight_max and count see the
+ *                  rays of nonzero weight).  Weights may be negative; weight_sum is then a signed sum.
+ *   out            device arrays [n] by original particle id; each may be NULL (that output is not computed), all three NULL:
+ *                  GRT_ERR_INVALID.  The outputs are ACCUMULATED into what the arrays hold — add, max, add — so several views sum up
+ *                  without a pass in between; the caller zeroes them.  weight_max must hold non-negative floats (it is updated by
+ *                  an unsigned-integer atomic max on their bit patterns).
+ * Skipped like in the backward: fisheye pixels with r > 1, pixels outside the window, rays the raygen loop does not trace
+ * (|d| <= 0.1, a NaN direction, max_bounces = 0).  With n = 0 rays, an empty window or an empty scene the call returns GRT_OK and
+ * writes nothing.  count and weight_max are BITWISE reproducible between calls (integer add, max); weight_sum is not (float atomics
+ * arrive in varying order; tests compare within a tolerance measured for float32 evaluation).  GRT_OPT_BWD_PLAIN_ATOMICS = 1 makes
+ * every lane issue its own atomics here too (testing).  The context owns no buffer for this: grt_memory_info::slot_bytes is
+ * unchanged by a call, and a frame rendered after a call is bit-identical to one rendered before it.  Asynchronous on `stream` like
+ * grt_render; grt_last_kernel_ms reports the call's device time.  A view computes the statistics of its scene.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): meshes set
+ * (statistics of mesh frames are not computed), GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a window outside the frame,
+ * sh_degree_max > 3, t_min <= 0.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB, as in the backward. */
+typedef struct {
+    float* weight_sum;
+    float* weight_max;
+    uint32_t* count;
+} grt_particle_stats;
+GRT_API int grt_particle_stats_frame(grt_ctx* ctx, const grt_params* p, const float* d_ray_weight /* may be NULL */,
+                                     const grt_particle_stats* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_particle_stats_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n,
+                                    const float* d_ray_weight /* may be NULL */, const grt_particle_stats* out, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
