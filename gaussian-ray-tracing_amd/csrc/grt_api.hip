@@ -497,7 +497,7 @@ static uint64_t faces_hash(uint64_t h, const uint32_t* f, size_t n)
     return h;
 }
 
-// The tile kernel's give-up reasons travel in the per-tile cost words (see the watchdog in grt_render_tile.hip): a cost
+// The tile kernel's give-up reasons travel in the per-tile cost words (see the watchdog in grt_tile.h): a cost
 // above the step watchdog = the watchdog fired, high bits = stack guard / two passes without progress.  One pass over
 // the costs right behind the frame ORs them into the context's sticky error word.
 // behind every frame (do_launch): error word and overflow demand to their pinned host words, overflow counter reset
@@ -1691,7 +1691,7 @@ static int prepare_feedback(grt_ctx* c, RenderArgs& a, hipStream_t s, uint32_t n
 }
 
 // The tile kernel's pool of window-overflow bags, in chunks of kTileOvfChunkBytes = 32 KiB (32 entries x 64 lanes): a tile that
-// overflows takes one to three in a row, by how deep its bags got in the frame before (grt_render_tile.hip kSub).  A tile that
+// overflows takes one to three in a row, by how deep its bags got in the frame before (grt_tile.h kSub).  A tile that
 // finds the pool empty falls back to another pass (never wrong; a pool for a quarter of the tiles ran dry on the default 1 M scene and
 // cost that frame 12 %, and on the needle scene C3a a pool of 3/8 of the tiles made the first frames 2.3 x slower).  Round 2 held a full
 // bag for EVERY tile of the launch for good (3.1 GB at 1080p, 12.4 GB at 4K, per frame slot); rounds 3-4 sized the pool from the

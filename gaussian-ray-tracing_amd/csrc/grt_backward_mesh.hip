@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_backward_mesh(const RenderArgs a, co
     const float minT = a.p.minTransmittance;
     const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
     KBuf<K> kb;
-    Cnt cnt; // (dead: no counters, no watchdog)
+    grt::Cnt cnt; // (dead: no counters, no watchdog)
     RayAcc ra; // (dead: RAYS = false)
     ra.go = ra.gd = ra.gdn = mk3(0, 0, 0);
 

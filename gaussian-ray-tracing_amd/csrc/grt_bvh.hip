@@ -590,7 +590,7 @@ __global__ __launch_bounds__(1024) void k_cost_order(const uint32_t* cost, uint3
 }
 
 // The chunks of the overflow pool a whole tile takes in the frame this order is made for, from the two lowest bits of its cost word
-// (grt_render_tile.hip kBagKeep1 / kBagKeep2: how full the fullest bag of any of its rays got): 1, 2 or 3 (a full bag); 0 = not known —
+// (grt_tile.h kBagKeep1 / kBagKeep2: how full the fullest bag of any of its rays got): 1, 2 or 3 (a full bag); 0 = not known —
 // a tile without a cost, or costs that are not the tile kernel's words at all (the cold frame's particle counts): the launch decides
 // (RenderArgs::ovf_cls0).  enabled = 0 (GRT_OPT_OVF_CLASSES off): a full bag for everyone
 __device__ __forceinline__ uint32_t bag_class(uint32_t enabled, uint32_t cost_word)
@@ -934,7 +934,7 @@ __global__ __launch_bounds__(1024) void k_ord_d(const uint32_t* cost, const uint
 uint32_t order_scratch_bytes() { return ord_scratch_words() * (uint32_t)sizeof(uint32_t); }
 
 // The four-way parts of a launch order as a list of their own, in the order's order (heaviest first): what the quad kernel
-// (grt_render_tile.hip MODE 3) takes, one wave per entry.  The first kQuadListCap of them are listed and re-coded 2 -> 3 in the order, so
+// (grt_tile.h MODE 3) takes, one wave per entry.  The first kQuadListCap of them are listed and re-coded 2 -> 3 in the order, so
 // that the camera-ray kernel leaves them alone; the rest stays as it is.  One workgroup, 1024 entries per round, ranks by ballot + a scan
 // of the 16 waves' counts; it runs behind the ordering kernel, i.e. behind the frame whose costs made the order — not in front of the
 // frame that uses it.

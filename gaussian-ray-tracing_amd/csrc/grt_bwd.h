@@ -22,6 +22,7 @@
 #include "grt_device.h"
 #include "grt_internal.h"
 #include "grt_kround.h"
+#include "grt_wave.h"
 
 namespace grt {
 namespace {
@@ -99,20 +100,6 @@ __device__ __forceinline__ void sh_basis(f3 d, uint32_t deg, float Y[16])
     Y[13] = (GRT_SH_C3_4 * x) * (4.0f * zz - xx - yy);
     Y[14] = (GRT_SH_C3_5 * z) * (xx - yy);
     Y[15] = (GRT_SH_C3_6 * x) * (xx - 3.0f * yy);
-}
-
-// sum over the wave of v (lanes outside `mine` hold 0), as a wave-uniform value
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));  // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));  // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)); // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true)); // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
 }
 
 // one lane's 14 values to its particle's row (geom: the 11 geometry / opacity values were formed; colour: the 3 colour values were)
@@ -341,7 +328,7 @@ __device__ __forceinline__ void backward_body(const RenderArgs& a, const BwdArgs
     const float minT = a.p.minTransmittance;
     const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
     KBuf<K> kb;
-    Cnt cnt; // (dead: no counters, no watchdog)
+    grt::Cnt cnt; // (dead: no counters, no watchdog; grt::Cnt is the round's, grt_kround.h — Cnt alone would be grt_wave.h's)
 
     // ---- two sweeps over the same events through ONE call site of the traversal (every lane of the wave in step: the scatter of
     //      sweep 1 is wave-cooperative).  Sweep 0: rad and T_end, trace() as the forward runs it (shaders/tracer.cuh:328-373);

@@ -34,7 +34,7 @@ struct DevBvh {
                                //   24 floats = 4 child boxes, each (lo.x lo.y | hi.x hi.y | lo.z hi.z),
                                //   W6 = 4 child refs, W7 pad; an unused child has ref kNoRoot
     float4* qnodes = nullptr;  // [(n_prims-1) * 2 * kTileWide] the tree laid out per CHILD for the tile kernel
-                               //   (grt_render_tile.hip: one lane tests one child box), kTileWide children per record:
+                               //   (grt_tile.h: one lane tests one child box), kTileWide children per record:
                                //   child c of node i at [i*2W + 2c] = (lo.xyz, ref bits), [+1] = (hi.xyz, 0); unused: ref kNoRoot
     float4* pbox = nullptr;    // [n_prims * 2] box of every sorted primitive, (lo.xyz,0)(hi.xyz,r), r = bounding radius about the box centre: what a leaf-range
                                //   child expands to in the tile kernel (built only for the Gaussian BVH)
@@ -116,7 +116,7 @@ struct RenderArgs {
     const uint32_t* n_heavy; // device count of leading blocks of `order` that run on the big-window kernel
     uint32_t heavy_role;     // 0 = every block, 1 = only ranks < *n_heavy, 2 = only ranks >= *n_heavy
     unsigned long long* counters; // kNumCounters x u64 or nullptr
-    // tile kernel tuning (grt_render_tile.hip)
+    // tile kernel tuning (grt_tile.h)
     uint32_t tile_ready_min; // lanes that must hold a final event before a compositing sweep starts
     float tile_band;         // particles within F * (1 + band) of the front are tested in one batch
     float tile_look;         // nodes within Fn * (1 + look) are expanded in one step
@@ -131,7 +131,7 @@ struct RenderArgs {
     uint32_t* ovf_next;      // next free chunk (zeroed before the launch)
     uint32_t ovf_chunks;     // chunks in the pool
     uint32_t ovf_entries;    // per-lane capacity of a bag actually used (<= kTileOvfEntries; smaller only in tests)
-    uint32_t ovf_cls0;       // chunks (1 or 3) a whole tile starts in when its order entry carries no size class (grt_render_tile.hip kSub)
+    uint32_t ovf_cls0;       // chunks (1 or 3) a whole tile starts in when its order entry carries no size class (grt_tile.h kSub)
     // always-on failure signal: a wave that has to give up on a ray (watchdog, stack guard, two passes without progress)
     // ORs its reason into this device word, whatever the kernel variant; grt_sync / grt_get_counters report it
     uint32_t* err_word;
@@ -191,15 +191,15 @@ struct AuxOut {
     float* depth;
     uint32_t* count;
 };
-int launch_render_tile_aux(const RenderArgs& a, const AuxOut& x, hipStream_t stream, std::string* err); // (its own TU)
+int launch_render_tile_aux(const RenderArgs& a, const AuxOut& x, hipStream_t stream, std::string* err); // (grt_render_tile_aux.hip)
 int launch_render(const RenderArgs& a, bool count, int kernel_variant, uint32_t stack_depth, bool tile_kernel,
                   hipStream_t stream, const LaunchAux* aux, std::string* err);
 int launch_render_wave(const RenderArgs& a, bool count, hipStream_t stream, std::string* err);
 int launch_render_stream(const RenderArgs& a, bool count, bool mesh, hipStream_t stream, const LaunchAux* aux,
                          std::string* err);
 int launch_render_tile(const RenderArgs& a, bool count, bool mesh, int mode, hipStream_t stream, std::string* err, const LaunchAux* aux = nullptr);
-int launch_render_tile_quad(const RenderArgs& a, bool count, hipStream_t stream, std::string* err); // mode 3 (its own TU)
-int launch_render_tile_single(const RenderArgs& a, bool count, hipStream_t stream, std::string* err); // mode 2 (its own TU)
+int launch_render_tile_quad(const RenderArgs& a, bool count, hipStream_t stream, std::string* err); // mode 3 (grt_render_tile_quad.hip)
+int launch_render_tile_single(const RenderArgs& a, bool count, hipStream_t stream, std::string* err); // mode 2 (grt_render_tile_single.hip)
 constexpr int kNumCounters = 8;
 // bits of RenderArgs::err_word
 constexpr uint32_t kErrWatchdog = 1u, kErrStack = 2u, kErrStall = 4u;
@@ -211,9 +211,9 @@ constexpr uint32_t kCostStackBit = 0x40000000u, kCostStallBit = 0x20000000u; // 
 // of the 1 M scene takes 0.79 of the whole tile's time, a half all of it), or a tile would be split on every other frame only.
 // (A larger factor inflates the split tiles' costs frame over frame until their parts no longer fit the launch.)
 // A WHOLE tile's entry (code 0) uses the part field for the size class of its overflow bags: the chunks of the pool it starts in (1, 2,
-// 3; 0 = no cost word yet), from the two lowest bits of its cost word (grt_render_tile.hip kBagKeep1 / kBagKeep2, grt_bvh.hip bag_class).
+// 3; 0 = no cost word yet), from the two lowest bits of its cost word (grt_tile.h kBagKeep1 / kBagKeep2, grt_bvh.hip bag_class).
 constexpr uint32_t kOrderUnitMask = 0x0FFFFFFFu, kOrderPad = 0xFFFFFFFFu;
-// code 3 = a four-way part that runs on the QUAD kernel (grt_render_tile.hip MODE 3): k_quad_list (grt_bvh.hip) re-codes the first
+// code 3 = a four-way part that runs on the QUAD kernel (grt_tile.h MODE 3): k_quad_list (grt_bvh.hip) re-codes the first
 // kQuadListCap four-way entries of an order and lists them for that kernel, whose grid is the list's capacity; what does not fit
 // stays code 2, a part wave of the camera-ray kernel.  (A part's unit is < 2^28, so code 3 | part 3 | unit never equals kOrderPad.)
 constexpr uint32_t kQuadListCap = 4096u;

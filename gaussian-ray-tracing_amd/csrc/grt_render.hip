@@ -173,7 +173,7 @@ __device__ __forceinline__ RayState fresh_ray(f3 o, f3 d)
 // stage 1 (this kernel): camera ray + mesh closest hit + closest-hit shading for every pixel, one record per thread
 //   prec[3*i+0] = (seg_tmax, flags, curO.x, curO.y)   flags = state | numBounces << 8 | have_ray << 16
 //   prec[3*i+1] = (curO.z, curD.x, curD.y, curD.z)     prec[3*i+2] = (normal.xyz, 0)
-// stage 2 (grt_render_tile.hip / grt_render_stream.hip, MESH = true): the coherent primary Gaussian segment
+// stage 2 (grt_tile.h / grt_render_stream.hip, MESH = true): the coherent primary Gaussian segment
 //   [t_min, seg_tmax] on the wave-per-tile kernel, first iteration of the compositing; the rays that go on are written
 //   to the continuation queue, one 64-entry chunk per tile (lane l in slot l)
 // stage 3, tile kernel only, bundle_rounds times: k_queue_mesh (the mesh hit of every queued ray, per lane; the mesh
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(kBlock) void k_primary_mesh_wave(const RenderArgs a
     }
 }
 
-// stage 4: finish the queued rays (queue record layout: grt_render_tile.hip / grt_render_stream_body.inc, MESH epilogue)
+// stage 4: finish the queued rays (queue record layout: grt_tile.h / grt_render_stream_body.inc, MESH epilogue)
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_bounce(const RenderArgs a)
 {
@@ -597,7 +597,7 @@ int launch_render(const RenderArgs& a, bool count, int kernel_variant, uint32_t 
             return GRT_ERR_HIP;
         }
         if (tile_kernel && a.mesh_primary_wave == 2u) {
-            // stage 1 runs inside stage 2 (grt_render_tile.hip, MODE 0 with MESH): no launch here
+            // stage 1 runs inside stage 2 (grt_tile.h, MODE 0 with MESH): no launch here
         } else if (a.mesh_primary_wave && a.mstack_depth) { // one walk of the mesh tree per 8x8 tile instead of one per lane
             auto fw = count ? k_primary_mesh_wave<true> : k_primary_mesh_wave<false>;
             hipLaunchKernelGGL(fw, dim3(a.n_blocks), dim3(kBlock), sizeof(uint32_t) * 4u * a.mstack_depth, stream, a);

@@ -446,7 +446,7 @@ __global__ __launch_bounds__(kWG, GRT_WAVES) void GRT_KERNEL_NAME(const RenderAr
     }
     if (MESH) {
         // ---- the rays that go on: the wave takes ONE 64-entry chunk of the queue (one atomic), every lane writes its own
-        //      slot; bit 31 of the timeout word marks the slots that carry a ray (same layout as grt_render_tile.hip) ----
+        //      slot; bit 31 of the timeout word marks the slots that carry a ray (same layout as grt_tile.h) ----
         const uint64_t mask = wave_ballot(cont);
         if (mask) { // wave-uniform
             uint32_t base = 0;

@@ -19,6 +19,7 @@
 
 #include "grt_device.h"
 #include "grt_internal.h"
+#include "grt_wave.h"
 
 namespace grt {
 
@@ -26,10 +27,6 @@ namespace {
 
 constexpr int K = 7; // MaxNumHitPerTrace, shaders/tracer.cuh:11
 constexpr int kBlock = 256;
-
-struct Cnt {
-    uint32_t rays = 0, segments = 0, hit_evals = 0, rounds = 0, node_visits = 0, proxy_tests = 0, fetches = 0, iters = 0;
-};
 
 struct KBuf {
     uint64_t key[K];
@@ -62,19 +59,6 @@ __device__ __forceinline__ bool kbuf_has(const KBuf& kb, uint64_t key)
     return h;
 }
 
-// scalar (SGPR) fetch of one float4 at a wave-uniform index: constant address space => s_load_dwordx4
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 sload4(const float4* base, uint32_t idx)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) v4f* cptr4;
-    const v4f v = ((cptr4)(uintptr_t)base)[idx];
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return base[idx];
-#endif
-}
-
 __device__ __forceinline__ uint32_t stack_pop(uint32_t s0, uint32_t s1, uint32_t sp)
 {
     return sp < 64u ? (uint32_t)__builtin_amdgcn_readlane((int)s0, (int)sp)
@@ -98,7 +82,7 @@ __device__ __forceinline__ void gps_round_wave(const RenderArgs& a, f3 o, f3 d, 
     uint32_t cur = a.root_ref;
     while (true) {
         cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur);
-        c.iters++;
+        c.stall_exits++; // (Cnt is grt_wave.h's: this kernel has no stall exits and keeps the walk's iterations, its cost word, in that field)
         if (cur & kLeafBit) {
             const uint32_t first = leaf_first(cur), cnt = leaf_count(cur);
             for (uint32_t j = 0; j < cnt; j++) {
@@ -288,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void k_render_wave(const RenderArgs a)
             a.out8[out_idx * 3 + 2] = quantize8(col.z);
         }
     }
-    if (a.cost && lane == 0) atomicMax(&a.cost[blk], c.iters);
+    if (a.cost && lane == 0) atomicMax(&a.cost[blk], c.stall_exits); // (the walk's iterations: gps_round_wave)
     if (COUNT) {
         // fetches are wave-level events: count them once per wave
         uint32_t v[7] = {c.rays, c.segments, c.hit_evals, c.rounds, c.node_visits, c.proxy_tests, 0};

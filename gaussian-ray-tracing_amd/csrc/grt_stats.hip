@@ -5,7 +5,7 @@
 // k_particle_stats<MERGE> is ONE sweep of the backward's body (grt_bwd.h: backward_body) without colour: lane_ray gives the ray, one
 // ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round (grt_kround.h) through a single call site, every lane of the wave in
 // step.  Per slot of the k-buffers the wave scatters as scatter<MERGE> does: the lanes that hold the same particle form a group
-// (ballot / readlane); the group's count is the popcount of its ballot, its sum wave_sum, its peak the same ladder with fmaxf, and
+// (ballot / readlane); the group's count is the popcount of its ballot, its sum wave_sum, its peak wave_max (grt_wave.h), and
 // its leader issues one atomic per requested output; a lane alone with its particle issues its own.  MERGE = false
 // (GRT_OPT_BWD_PLAIN_ATOMICS = 1): every lane issues its own.  The atomics go straight into the caller's arrays: float add,
 // unsigned max on the bit pattern of a non-negative float, unsigned add.  The context owns no buffer for this.
@@ -25,20 +25,6 @@ struct StatsArgs {
     float* weight_max;       // [n] or null
     uint32_t* count;         // [n] or null
 };
-
-// max over the wave of v >= 0 (lanes outside the group hold 0), as a wave-uniform value: wave_sum's ladder (grt_bwd.h) with fmaxf
-__device__ __forceinline__ float wave_max(float v)
-{
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));  // quad_perm [1,0,3,2]
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));  // quad_perm [2,3,0,1]
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true))); // row_half_mirror
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true))); // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
 
 // one atomic per requested output (the branches are wave-uniform: kernel arguments)
 __device__ __forceinline__ void stats_add(const StatsArgs& s, uint32_t id, float sum, float peak, uint32_t n)
@@ -102,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, c
     const float t_hi = t_max + epsT;
     const float minT = a.p.minTransmittance;
     KBuf<K> kb;
-    Cnt cnt; // (dead: no counters, no watchdog)
+    grt::Cnt cnt; // (dead: no counters, no watchdog)
 
     // one sweep over the events trace() composites (shaders/tracer.cuh:328-373), every lane of the wave in step: the scatter is
     // wave-cooperative, a finished lane idles

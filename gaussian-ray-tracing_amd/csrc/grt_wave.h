@@ -1,5 +1,6 @@
-// grt_wave.h — wave64-level building blocks shared by the wave-cooperative render kernels (gfx950 only):
-// scalar (constant-address-space) record fetches, DPP min reductions, lane-mask votes, slot-key packing.
+// grt_wave.h — wave64-level building blocks shared by the wave-cooperative render kernels, the backward pass and the particle
+// statistics (gfx950 only): scalar (constant-address-space) record fetches, DPP reductions (min, sum, max; signed floats and 64-bit
+// keys through integer keys), lane-mask votes, lane reads, slot-key packing.  The one home of such helpers: a unit defines none.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@ struct Cnt {
     uint32_t rays = 0, segments = 0, hit_evals = 0, rounds = 0, node_visits = 0, proxy_tests = 0, fetches = 0, stall_exits = 0;
 };
 
+// scalar (SGPR) fetch of one float4 at a wave-uniform index: constant address space => s_load_dwordx4
 typedef float v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 sload4(const float4* base, uint32_t idx)
 {
@@ -79,6 +81,34 @@ __device__ __forceinline__ float wave_min(float v)
 #endif
 }
 
+// sum over the wave of v (lanes outside `mine` hold 0), as a wave-uniform value
+__device__ __forceinline__ float wave_sum(float v)
+{
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));  // quad_perm [1,0,3,2]
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));  // quad_perm [2,3,0,1]
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)); // row_half_mirror
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true)); // row_mirror
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return (r0 + r1) + (r2 + r3);
+}
+
+// max over the wave of v >= 0 (lanes outside the group hold 0), as a wave-uniform value: wave_sum's ladder with fmaxf
+__device__ __forceinline__ float wave_max(float v)
+{
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));  // quad_perm [1,0,3,2]
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));  // quad_perm [2,3,0,1]
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true))); // row_half_mirror
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true))); // row_mirror
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+
 // four independent wave minima in lockstep: the DPP steps of different reductions interleave, so the two wait states a
 // DPP operand needs after its producer are filled with useful work instead of s_nop
 __device__ __forceinline__ void wave_min4(float a, float b, float c, float d, float& ra, float& rb, float& rc, float& rd)
@@ -105,6 +135,91 @@ __device__ __forceinline__ void wave_min4(float a, float b, float c, float d, fl
 #undef GRT_ROWS
 #else
     ra = a; rb = b; rc = c; rd = d;
+#endif
+}
+
+// Signed-float wave reductions (the tile kernel, grt_tile.h): eleven per frustum fit, and a tile re-fits its frustum every time half of its wanting lanes
+// have finished.  As `fminf(v, __shfl_xor(v, off))` each was six dependent LDS round trips (ds_bpermute) and eighteen VALU
+// operations with their NaN canonicalisation; here a float goes through an order-preserving integer key (sign bit
+// flipped for v >= 0, all bits for v < 0), the DPP integer minimum above (wave_min / wave_min4: no LDS, four
+// reductions interleaved) and back.  The result is wave-uniform and the exact minimum / maximum as before.
+// NaN: unlike fminf / fmaxf the integer key does not drop it (a NaN would win the reduction and void the frustum for the
+// whole tile).  No NaN reaches these reductions: they are fed from the rays of lanes with `alive`, which implies
+// have_ray, i.e. length(d) > 0.1 (the reference's loop guard, shaders/tracer.cu:59 — false for a NaN direction, which is
+// how a bounce off a zero shading normal ends), with origins that are the eye or a finite mesh hit point
+// (tests/test_gpu_parity.py::test_mesh_with_zero_normals_nan_bounce_directions).
+__device__ __forceinline__ uint32_t fkey(float f)
+{
+    const uint32_t b = __float_as_uint(f);
+    return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(uint32_t k)
+{
+    return __uint_as_float(k ^ ((uint32_t)((int32_t)~k >> 31) | 0x80000000u));
+}
+__device__ __forceinline__ float wave_fmin(float v) { return fkey_inv(__float_as_uint(wave_min(__uint_as_float(fkey(v))))); }
+__device__ __forceinline__ float wave_fmax(float v) { return fkey_inv(~__float_as_uint(wave_min(__uint_as_float(~fkey(v))))); }
+// (min a, max b, min c, max d) in one go
+__device__ __forceinline__ void wave_fminmax4(float a, float b, float c, float d, float& mna, float& mxb, float& mnc, float& mxd)
+{
+    float ra, rb, rc, rd;
+    wave_min4(__uint_as_float(fkey(a)), __uint_as_float(~fkey(b)), __uint_as_float(fkey(c)), __uint_as_float(~fkey(d)), ra, rb, rc, rd);
+    mna = fkey_inv(__float_as_uint(ra)); mxb = fkey_inv(~__float_as_uint(rb));
+    mnc = fkey_inv(__float_as_uint(rc)); mxd = fkey_inv(~__float_as_uint(rd));
+}
+__device__ __forceinline__ float uni(float v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v)));
+#else
+    return v;
+#endif
+}
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) // number of set bits of m below this lane
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+#else
+    return 0u;
+#endif
+}
+// wave64 minimum of 64-bit keys (two unsigned 32-bit DPP reductions: wave_min works on the bit patterns)
+__device__ __forceinline__ uint64_t wave_umin64(uint64_t k)
+{
+    const uint32_t hi = (uint32_t)(k >> 32);
+    const uint32_t mh = __float_as_uint(wave_min(__uint_as_float(hi)));
+    const uint32_t lo = (hi == mh) ? (uint32_t)k : 0xFFFFFFFFu;
+    const uint32_t ml = __float_as_uint(wave_min(__uint_as_float(lo)));
+    return ((uint64_t)mh << 32) | (uint64_t)ml;
+}
+// minimum of 64-bit keys over the four lanes of a quad (lanes 4 q .. 4 q + 3), in every lane of the quad: the high words by two
+// DPP minima, then the low words of the lanes that hold that high word
+__device__ __forceinline__ uint64_t quad_umin64(uint64_t k)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t hi = (uint32_t)(k >> 32);
+    uint32_t mh = min(hi, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0xB1, 0xF, 0xF, true)); // quad_perm [1,0,3,2]
+    mh = min(mh, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mh, 0x4E, 0xF, 0xF, true));           // quad_perm [2,3,0,1]
+    const uint32_t lo = (hi == mh) ? (uint32_t)k : 0xFFFFFFFFu;
+    uint32_t ml = min(lo, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, 0xB1, 0xF, 0xF, true));
+    ml = min(ml, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)ml, 0x4E, 0xF, 0xF, true));
+    return ((uint64_t)mh << 32) | (uint64_t)ml;
+#else
+    return k;
+#endif
+}
+__device__ __forceinline__ float lane_value(float v, int l) // v of lane l (l wave-uniform)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), l));
+#else
+    return v;
+#endif
+}
+__device__ __forceinline__ void wave_fence()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // compiler ordering of the LDS exchange; no instruction
 #endif
 }
 

@@ -135,7 +135,7 @@ typedef struct {
 } grt_memory_info;
 
 enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_counters */,
-       GRT_OPT_KERNEL = 2   /* 0 = auto: camera-ray frames on the tile kernel (grt_render_tile.hip: BVH culling per child box
+       GRT_OPT_KERNEL = 2   /* 0 = auto: camera-ray frames on the tile kernel (csrc/grt_tile.h: BVH culling per child box
                                against the tile frustum; also stage 2 of the wavefront pipeline of mesh frames) — or on the
                                streaming kernel when the BVH was built with GRT_OPT_LEAF_MAX > 4; ray buffers on the per-lane kernel.
                                1 = per-lane kernel everywhere, 2 = round-based wave kernel for camera rays without meshes

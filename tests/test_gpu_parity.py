@@ -569,7 +569,7 @@ def test_bounce_pipeline_every_route_gives_the_same_frame(mesh_type, sh_degree):
 def test_camera_inside_a_dense_cluster_full_bags_are_pruned():
     """The eye sits in the densest cell of the scene, inside hundreds of overlapping proxies: their exit events are all
     pending at once and arrive in no order, every lane's window overflows into its bag, full bags keep their nearer half
-    (grt_render_tile.hip: bag_prune) and some lanes still go again.  Tile kernel == streaming kernel == per-lane kernel
+    (grt_tile.h: bag_prune) and some lanes still go again.  Tile kernel == streaming kernel == per-lane kernel
     bit for bit, and the oracle within tolerance."""
     W, H = 160, 128
     acts, p0, sc, op0, center = make_scene(61, 60000, W, H, scale_boost=1.3)

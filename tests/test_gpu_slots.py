@@ -74,7 +74,7 @@ def test_views_share_one_scene_and_render_the_same_frames():
 
 def test_overflow_pool_follows_demand_and_tolerates_exhaustion():
     """The pool of window-overflow bags: sized from the demand of the frames before; with too few chunks (or none) the
-    tiles that find it empty drop events for good and go again (grt_render_tile.hip: `dry`) — more
+    tiles that find it empty drop events for good and go again (grt_tile.h: `dry`) — more
     passes, the same bytes."""
     acts, p, sc = _dense_cluster_camera()
     tr = grt.Tracer(0)
@@ -118,7 +118,7 @@ def test_tiles_with_shallow_bags_take_one_chunk_of_the_pool():
     """The pool is handed out in chunks of 32 entries x 64 rays.  A tile STARTS in one, two or three in a row (three: a full
     96-entry bag per ray) by how deep its bags got in the frame before — the tile kernel notes that in the two lowest bits of
     the tile's cost word, the launch order hands the size class back in the part field of a whole tile's entry
-    (grt_render_tile.hip kBagKeep1 / kBagKeep2, grt_bvh.hip bag_class); a tile without a cost word starts in one; a tile that
+    (grt_tile.h kBagKeep1 / kBagKeep2, grt_bvh.hip bag_class); a tile without a cost word starts in one; a tile that
     outgrows its chunks moves to three fresh ones (its rays' entries are copied).  Same frames whatever the classes, a
     smaller demand than with a full bag for everyone, and a camera that moves — tiles changing class every frame — renders
     what a tracer without feedback renders."""

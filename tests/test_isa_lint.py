@@ -284,12 +284,12 @@ def _built_asm():
 
 def test_shipped_assembly_has_no_spill_code_in_front_of_an_exec_restore():
     names = {os.path.basename(f) for f in _built_asm()}
-    assert {"grt_render_tile.s", "grt_render_tile_single.s", "grt_render_tile_quad.s", "grt_render_stream.s", "grt_render.s", "grt_render_wave.s", "grt_bvh.s", "grt_api.s"} <= names
+    assert {"grt_render_tile.s", "grt_render_tile_single.s", "grt_render_tile_quad.s", "grt_render_tile_aux.s", "grt_render_stream.s", "grt_render.s", "grt_render_wave.s", "grt_bvh.s", "grt_api.s"} <= names
     for f in _built_asm():
         assert V.lint(open(f).read()) == [], os.path.basename(f)
 
 
-def _budget():
+def _budget_rows():
     """the budget of the assembly that is there NOW: the JSON is a build artefact beside it, made again when any kept .s is newer"""
     files = _built_asm()
     p = os.path.join(CSRC, "build_asm", "isa_budget.json")
@@ -297,7 +297,11 @@ def _budget():
         import subprocess
         marks = os.path.join(CSRC, "build_asm", "grt_render_tile_marks.s")
         subprocess.check_call([sys.executable, os.path.join(ROOT, "profiles", "isa_budget_current.py")] + (["--marks", marks] if os.path.exists(marks) else []))
-    return {k["kernel"]: k for k in json.load(open(p))["kernels"]}
+    return json.load(open(p))["kernels"]
+
+
+def _budget():
+    return {k["kernel"]: k for k in _budget_rows()}
 
 
 def test_isa_budget_of_the_render_kernels():
@@ -345,6 +349,30 @@ def test_isa_budget_of_the_render_kernels():
     assert m1["spill_instructions_in_loops"] <= 30 and m2["lane_moves_in_loops"] <= 390 and m2["spill_instructions"] == 0, (m1, m2)
     c5 = b["grt::k_render_tile<false, false, false, 0, true>"]  # the same with pieces (needle / sheet scenes)
     assert c5["spill_instructions_in_loops"] <= 2 and c5["spill_instructions"] <= 16, c5  # (two in its piece-ownership block)
+
+
+def test_each_tile_unit_holds_the_instantiations_of_its_own_modes_and_no_others():
+    """The tile kernel's text (csrc/grt_tile.h) is compiled by four units, each for the occupancy its modes need; a unit's picker
+    decides what it instantiates: grt_render_tile.hip 2 (COUNT) x 2 (SH) x 2 (PIECES) x 3 (camera rays, camera rays of mesh frames,
+    bundles), the single unit 2 x 2 x 2, the quad unit 2 x 2, the aux unit 2 (SH) x 2 (PIECES).  A unit that instantiates a mode it
+    was split off to avoid compiles that mode for the wrong register budget, and the library then holds the kernel twice."""
+    per_unit = {}
+    for k in _budget_rows():
+        if "k_render_tile" in k["kernel"]:
+            per_unit.setdefault(k["file"], []).append(k["kernel"])
+    assert set(per_unit) == {"grt_render_tile.s", "grt_render_tile_single.s", "grt_render_tile_quad.s", "grt_render_tile_aux.s"}, sorted(per_unit)
+
+    def modes(unit):
+        names = per_unit[unit]
+        assert all("k_render_tile<" in n for n in names) and len(set(names)) == len(names), (unit, names)
+        return sorted(int(re.search(r"k_render_tile<\w+, \w+, \w+, (\d)", n).group(1)) for n in names)
+
+    m = modes("grt_render_tile.s")
+    assert len(m) == 24 and set(m) == {0, 1}, m
+    assert modes("grt_render_tile_single.s") == [2] * 8
+    assert modes("grt_render_tile_quad.s") == [3] * 4
+    aux = per_unit["grt_render_tile_aux.s"]
+    assert len(set(aux)) == len(aux) == 4 and all("k_render_tile_aux<" in n and "k_render_tile<" not in n for n in aux), aux
 
 
 def test_non_default_configurations_of_the_tile_kernel_compile_and_pass_the_lints(tmp_path):
