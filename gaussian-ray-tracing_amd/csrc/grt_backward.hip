@@ -3,7 +3,7 @@
 //
 // The device text is grt_bwd.h; this unit instantiates k_backward<MERGE> from it and holds what exists once for the three backward
 // units: the flush kernels, the context's gradient buffers, and the host path every entry point takes (grt_internal.h: bwd_fill_args,
-// bwd_set_window, bwd_set_rays, bwd_launch).
+// bwd_launch; the work mappings set_window and set_rays are grt_frame.hip's).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -50,15 +50,6 @@ __global__ __launch_bounds__(256) void k_bwd_flush_sh(float* __restrict__ acc_sh
 } // namespace grt
 
 using namespace grt;
-
-#define CHK(ctx, x)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) {                                                                       \
-            (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"; \
-            return GRT_ERR_HIP;                                                                       \
-        }                                                                                             \
-    } while (0)
 
 // The context's gradient buffers for n particles (hi: the higher-SH buffer as well), zeroed when new; a backward on another stream
 // than the last one's waits for that one's flush (the buffers belong to the context).
@@ -109,7 +100,7 @@ int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, con
 {
     if (!c) return GRT_ERR_INVALID;
     if (!p) { c->err = std::string(fn) + ": null parameters"; return GRT_ERR_INVALID; }
-    const grt_ctx* sc = c->parent ? c->parent : c;
+    const grt_ctx* sc = scene_of(c);
     if (!sc->built) { c->err = std::string(fn) + ": grt_build_bvh has not been called after the last upload"; return GRT_ERR_INVALID; }
     if (!mesh && sc->n_faces) { c->err = std::string(fn) + ": meshes are set (grt_backward_mesh / grt_backward_rays_mesh differentiate mesh frames)"; return GRT_ERR_INVALID; }
     if (c->opt_counters) { c->err = std::string(fn) + ": GRT_OPT_COUNTERS = 1 (the backward kernel is not instrumented)"; return GRT_ERR_INVALID; }
@@ -126,7 +117,7 @@ int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, con
     a->color0 = sc->d_color0;
     a->sh = sc->d_sh;
     a->mroot = kNoRoot;
-    if (mesh) { // the mesh side, as the per-lane aux launch has it (grt_api.hip: fill_common)
+    if (mesh) { // the mesh side, as the per-lane aux launch has it (grt_frame.hip: fill_common)
         a->mnodes = sc->mbvh.nodes;
         a->tri = sc->d_tri;
         a->mroot = sc->n_faces ? sc->mbvh.root_ref : kNoRoot;
@@ -139,31 +130,10 @@ int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, con
     return GRT_OK;
 }
 
-int bwd_set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const char* fn)
-{
-    if (x1 > p->width || y1 > p->height || x0 > x1 || y0 > y1) { c->err = std::string(fn) + ": window outside the frame"; return GRT_ERR_INVALID; }
-    a->mode = 0;
-    a->x0 = x0; a->y0 = y0; a->x1 = x1; a->y1 = y1;
-    a->nbx = (x1 - x0 + 15) / 16;
-    a->nby = (y1 - y0 + 15) / 16;
-    a->n_blocks = a->nbx * a->nby;
-    return GRT_OK;
-}
-
-int bwd_set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const char* fn)
-{
-    if (n && !d_rays) { c->err = std::string(fn) + ": null ray buffer"; return GRT_ERR_INVALID; }
-    if (n > 0xFFFFFFFFull * 64) { c->err = std::string(fn) + ": too many rays"; return GRT_ERR_LIMIT; }
-    a->mode = 2;
-    a->rays = d_rays; a->n_rays = n;
-    a->n_blocks = (uint32_t)((n + 255) / 256);
-    return GRT_OK;
-}
-
 int bwd_launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha,
                const grt_gaussian_grads* g, float* d_ray_grads, const void* const kernels[3], void* stream, const char* fn)
 {
-    const grt_ctx* sc = c->parent ? c->parent : c;
+    const grt_ctx* sc = scene_of(c);
     const uint64_t n = sc->n;
     const bool want_geom = g && (g->pos || g->scale || g->quat || g->opacity);
     const bool want_sh = g && g->sh;
@@ -220,7 +190,7 @@ int grt_backward(grt_ctx* c, const grt_params* p, const float* d_rgbf, const flo
     const char* fn = "grt_backward";
     RenderArgs a;
     int rc = bwd_fill_args(c, p, false, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
+    if (rc == GRT_OK) rc = set_window(c, p, &a, x0, y0, x1, y1, fn);
     if (rc != GRT_OK) return rc;
     return launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, g, stream, fn);
 }
@@ -231,7 +201,7 @@ int grt_backward_rays(grt_ctx* c, const grt_params* p, const float* d_rays, uint
     const char* fn = "grt_backward_rays";
     RenderArgs a;
     int rc = bwd_fill_args(c, p, false, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
+    if (rc == GRT_OK) rc = set_rays(c, &a, d_rays, n, fn);
     if (rc != GRT_OK) return rc;
     if (n == 0) { // (no ray: nothing to read either)
         if (!g) { c->err = "grt_backward_rays: null grads structure"; return GRT_ERR_INVALID; }

@@ -219,7 +219,7 @@ int grt_backward_mesh(grt_ctx* c, const grt_params* p, const float* d_grad_rgbf,
     const char* fn = "grt_backward_mesh";
     RenderArgs a;
     int rc = bwd_fill_args(c, p, true, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
+    if (rc == GRT_OK) rc = set_window(c, p, &a, x0, y0, x1, y1, fn);
     if (rc != GRT_OK) return rc;
     return launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, stream, fn);
 }
@@ -230,7 +230,7 @@ int grt_backward_rays_mesh(grt_ctx* c, const grt_params* p, const float* d_rays,
     const char* fn = "grt_backward_rays_mesh";
     RenderArgs a;
     int rc = bwd_fill_args(c, p, true, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
+    if (rc == GRT_OK) rc = set_rays(c, &a, d_rays, n, fn);
     if (rc != GRT_OK) return rc;
     if (n == 0) { // (no ray: nothing to read either)
         if (!g) { c->err = "grt_backward_rays_mesh: null grads structure"; return GRT_ERR_INVALID; }

@@ -42,7 +42,7 @@ int grt_backward_ex(grt_ctx* c, const grt_params* p, const float* d_rgbf, const 
     if (!out->rays) return grt_backward(c, p, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, out->gaussians, x0, y0, x1, y1, stream);
     RenderArgs a;
     int rc = bwd_fill_args(c, p, false, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
+    if (rc == GRT_OK) rc = set_window(c, p, &a, x0, y0, x1, y1, fn);
     if (rc != GRT_OK) return rc;
     return launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, out, stream, fn);
 }
@@ -56,7 +56,7 @@ int grt_backward_rays_ex(grt_ctx* c, const grt_params* p, const float* d_rays, u
     if (!out->rays) return grt_backward_rays(c, p, d_rays, n, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, out->gaussians, stream);
     RenderArgs a;
     int rc = bwd_fill_args(c, p, false, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
+    if (rc == GRT_OK) rc = set_rays(c, &a, d_rays, n, fn);
     if (rc != GRT_OK) return rc;
     return launch(c, p, a, d_rgbf, d_alpha, d_grad_rgbf, d_grad_alpha, out, stream, fn);
 }

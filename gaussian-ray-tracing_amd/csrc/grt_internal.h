@@ -78,7 +78,7 @@ struct RenderArgs {
     grt_params p;
     // Gaussian scene
     const float4* rec;    // [n_prox*4] Morton-sorted proxy records (see grt_api.hip: k_gather_records)
-    const float4* erec;   // per-eye part of the proxy test, same order; camera frames only: [n_prox] (k_eye_records) for the
+    const float4* erec;   // per-eye part of the proxy test, same order; camera frames only: [n_prox] (grt_frame.hip: k_eye_records) for the
                           // streaming kernel, [n_prox*4] (k_eye_records_wide) for the tile kernel
     const float4* nodes;
     const float4* wnodes; // 4-wide records (streaming kernel)
@@ -353,7 +353,7 @@ struct grt_ctx {
     float alpha_min = 0.01f;
     grt::DevBvh gbvh;
     float4* d_rec = nullptr;
-    float4* d_erec = nullptr;   // per-eye records of the streaming kernel (grt_api.hip: k_eye_records)
+    float4* d_erec = nullptr;   // per-eye records of the streaming kernel (grt_frame.hip: k_eye_records)
     float4* d_erec_wide = nullptr; // 64-B eye records of the tile kernel (k_eye_records_wide)
     size_t cap_erec_wide = 0, cap_erec = 0;
     bool erec_is_wide = false;
@@ -375,7 +375,7 @@ struct grt_ctx {
     unsigned long long* d_counters = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_timing = false;
-    // frame-to-frame scheduling feedback (grt_api.hip: do_launch)
+    // frame-to-frame scheduling feedback (grt_frame.hip: do_launch)
     int opt_feedback = 1;
     uint32_t *d_cost = nullptr, *d_order = nullptr, *d_cost_dil = nullptr, *d_ord_scratch = nullptr;
     uint32_t *d_qparts = nullptr, *d_qpcount = nullptr; // the order's four-way parts as a list for the quad kernel (allocated with d_order)
@@ -446,15 +446,31 @@ struct grt_ctx {
     hipEvent_t ev_upd0 = nullptr, ev_upd1 = nullptr;
 };
 
+// a failed HIP call: its text, the error and where it was made go to the context's error string, the function returns GRT_ERR_HIP
+#define CHK(ctx, x)                                                                                   \
+    do {                                                                                              \
+        hipError_t e_ = (x);                                                                          \
+        if (e_ != hipSuccess) {                                                                       \
+            (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"; \
+            return GRT_ERR_HIP;                                                                       \
+        }                                                                                             \
+    } while (0)
+
 namespace grt {
+// the context that owns the scene a context renders: itself, or a view's parent
+inline grt_ctx* scene_of(grt_ctx* c) { return c->parent ? c->parent : c; }
+inline const grt_ctx* scene_of(const grt_ctx* c) { return c->parent ? c->parent : c; }
+// grt_frame.hip: everything a frame slot owns (a view has nothing else), freed; for grt_api.hip's grt_create / destroy_now
+void free_slot_state(grt_ctx* c);
+// grt_frame.hip: the work mapping of a frame, a backward pass or a statistics pass — a window of the frame (refused when outside it), or a
+// ray buffer (refused when null, or too long).  Each returns GRT_OK or the refusal's code, its text in c->err with the entry point's name `fn` in front.
+int set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const char* fn);
+int set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const char* fn);
 // grt_backward.hip: the host path of the backward entry points (grt_backward*.hip).  Each returns GRT_OK or the refusal's code, its
 // text in c->err with the entry point's name `fn` in front.
 // The arguments every backward kernel reads, after the refusals all entry points share (null p, no BVH, counters on, sh_degree_max,
 // t_min).  mesh: the mesh side is filled and p->type checked; without it a scene with meshes is refused.
 int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn);
-// The work mapping: a window of the frame (refused when outside it), or a ray buffer (refused when null, or too long).
-int bwd_set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const char* fn);
-int bwd_set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const char* fn);
 // The launch: gradient buffers, LDS stack, the kernel between ev0 and ev1, the flush.  kernels: the calling unit's instantiations —
 // [0] the one that scatters nothing (runs when there is a per-ray output d_ray_grads and no Gaussian gradient to form; else null),
 // [1] plain atomics, [2] the wave merge — each taking (RenderArgs, BwdArgs) or (RenderArgs, BwdArgs, RayOut) of grt_bwd.h.

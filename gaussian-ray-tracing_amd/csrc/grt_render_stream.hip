@@ -4,7 +4,7 @@
 // wave64 = one 8x8 pixel tile, and the k = 7 re-traversal rounds of trace() (shaders/tracer.cuh:341-369) are replaced
 // by ONE front-to-back pass over the 4-wide view of the LBVH (grt_bvh.hip: k_widen):
 //   * records are fetched once per wave with scalar loads: a 128-B wide node, or a 64-B proxy record plus the 16-B
-//     per-eye record that holds what depends on the ray origin only (grt_api.hip: k_eye_records);
+//     per-eye record that holds what depends on the ray origin only (grt_frame.hip: k_eye_records);
 //   * the wave expands the tree BEST-FIRST: the frontier (unexpanded subtrees) lives in wave registers — slot i is
 //     lane i of one (lambda, ref) VGPR pair, 64 slots — keyed by lambda = the smallest box-entry distance over the
 //     lanes that want the subtree; pop = DPP min-reduction + ballot + v_readlane.  A full frontier spills to a

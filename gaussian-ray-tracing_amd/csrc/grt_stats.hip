@@ -135,20 +135,11 @@ __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, c
 
 using namespace grt;
 
-#define CHK(ctx, x)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (x);                                                                          \
-        if (e_ != hipSuccess) {                                                                       \
-            (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"; \
-            return GRT_ERR_HIP;                                                                       \
-        }                                                                                             \
-    } while (0)
-
 // what both entry points refuse before they look at their rays: the backward's refusals in the entry point's name, and a scene with meshes
 static int fill(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
 {
     if (!c) return GRT_ERR_INVALID;
-    const grt_ctx* sc = c->parent ? c->parent : c;
+    const grt_ctx* sc = scene_of(c);
     if (p && sc->built && sc->n_faces) {
         c->err = std::string(fn) + ": meshes are set (particle statistics are computed for Gaussian-only frames)";
         return GRT_ERR_INVALID;
@@ -162,7 +153,7 @@ static int launch(grt_ctx* c, const RenderArgs& a, const float* d_ray_weight, co
         c->err = std::string(fn) + ": no output (weight_sum, weight_max and count are all NULL)";
         return GRT_ERR_INVALID;
     }
-    const grt_ctx* sc = c->parent ? c->parent : c;
+    const grt_ctx* sc = scene_of(c);
     // no ray, no particle or an empty tree: nothing is composited, nothing is written
     if (a.n_blocks == 0 || sc->n == 0 || sc->gbvh.root_ref == kNoRoot) { c->have_timing = false; return GRT_OK; }
     CHK(c, hipSetDevice(c->device));
@@ -192,7 +183,7 @@ int grt_particle_stats_frame(grt_ctx* c, const grt_params* p, const float* d_ray
     const char* fn = "grt_particle_stats_frame";
     RenderArgs a;
     int rc = fill(c, p, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_window(c, p, &a, x0, y0, x1, y1, fn);
+    if (rc == GRT_OK) rc = set_window(c, p, &a, x0, y0, x1, y1, fn);
     if (rc != GRT_OK) return rc;
     return launch(c, a, d_ray_weight, out, stream, fn);
 }
@@ -203,7 +194,7 @@ int grt_particle_stats_rays(grt_ctx* c, const grt_params* p, const float* d_rays
     const char* fn = "grt_particle_stats_rays";
     RenderArgs a;
     int rc = fill(c, p, &a, fn);
-    if (rc == GRT_OK) rc = bwd_set_rays(c, &a, d_rays, n, fn);
+    if (rc == GRT_OK) rc = set_rays(c, &a, d_rays, n, fn);
     if (rc != GRT_OK) return rc;
     return launch(c, a, d_ray_weight, out, stream, fn);
 }

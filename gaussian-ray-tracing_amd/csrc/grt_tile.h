@@ -993,7 +993,7 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                 // store to an error word from this kernel (in the loop, behind it, atomic or plain) re-shuffled the register
                 // allocation of the hot loop and cost MODE 0 12-16 % (2.18 -> 2.44-2.53 ms on C3, six formulations measured).
                 // So a camera-ray tile's reasons travel in the cost word it writes anyway (iters > max_iters = watchdog, high
-                // bits = stack guard / stalled passes) and k_check_costs (grt_api.hip) turns them into the sticky error
+                // bits = stack guard / stalled passes) and k_check_costs (grt_frame.hip) turns them into the sticky error
                 // word right behind the frame.  A bundle (MODE 1) in trouble gives up as if over budget and its rays go one
                 // per wave; that last resort (MODE 2: 2 waves per SIMD, registers to spare) reports directly.
                 if (++iters > a.max_iters) {
