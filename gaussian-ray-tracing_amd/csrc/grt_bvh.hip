@@ -1006,6 +1006,9 @@ int order_units_with_parts(const uint32_t* d_cost_order, const uint32_t* d_cost_
 // Under a MOVING camera a heavy tile of the previous frame is a slightly different tile of this one: every 8x8 tile
 // takes the largest cost within `radius` tiles of itself, so the neighbourhood of last frame's heavy tiles starts
 // early too.  Units are (16x16 block, quadrant): block b = by * nbx + bx, quadrant q -> tile (2 bx + (q & 1), 2 by + (q >> 1)).
+// The output is a cost_eff VALUE (with the neighbourhood's deepest bag bits), not a cost word with a part code; the ordering kernels read
+// it through cost_eff like every ordering word, which is the identity while the value is below 2^27 — step counts up to 2^27 / 1.25, fifty
+// times the default watchdog.  Above that its bits 27-28 would be taken for a code: a wrong CLASS for a tile that ran for minutes.
 __global__ void k_cost_dilate(const uint32_t* __restrict__ cost, uint32_t* __restrict__ out, uint32_t nbx, uint32_t nby, int radius)
 {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;

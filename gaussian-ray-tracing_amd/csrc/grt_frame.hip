@@ -189,6 +189,26 @@ int grt::set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0,
     return GRT_OK;
 }
 
+// the tile list of grt_render_tiles (has_out: the caller has somewhere to put the pixels; refused between the two geometry tests, where
+// that entry point has always refused it)
+static int set_tiles(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t tile_w, uint32_t tile_h, uint32_t first_tile, uint32_t tile_stride,
+                     uint32_t n_tiles, bool has_out, const char* fn)
+{
+    if (!tile_w || !tile_h || (tile_w % 16) || (tile_h % 16)) { c->err = std::string(fn) + ": tile size must be a multiple of 16"; return GRT_ERR_INVALID; }
+    if (!has_out) { c->err = std::string(fn) + ": no output buffer"; return GRT_ERR_INVALID; }
+    const uint32_t tiles_x = (p->width + tile_w - 1) / tile_w, tiles_y = (p->height + tile_h - 1) / tile_h;
+    if (n_tiles && (!tile_stride || (uint64_t)first_tile + (uint64_t)(n_tiles - 1) * tile_stride >= (uint64_t)tiles_x * tiles_y)) {
+        c->err = std::string(fn) + ": tile range outside the frame's tile grid";
+        return GRT_ERR_INVALID;
+    }
+    a->mode = 1;
+    a->tile_w = tile_w; a->tile_h = tile_h; a->first_tile = first_tile; a->tile_stride = tile_stride; a->n_tiles = n_tiles;
+    a->tiles_x = tiles_x;
+    a->nbx = tile_w / 16; a->nby = tile_h / 16;
+    a->n_blocks = n_tiles * a->nbx * a->nby;
+    return GRT_OK;
+}
+
 int grt::set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const char* fn)
 {
     if (n && !d_rays) { c->err = std::string(fn) + ": null ray buffer"; return GRT_ERR_INVALID; }
@@ -243,11 +263,11 @@ static bool quad_parts_ok(const grt_ctx* c, uint32_t n_units)
 }
 // the four-way threshold such launches use: parts on the quad kernel cost a third of what part waves of the camera-ray kernel cost, so
 // more tiles are worth splitting the fewer tiles there are per resident wave — pct4 at two tiles per wave, half of it at one and below
-static uint32_t quad_pct4(const grt_ctx* c, uint32_t n_units)
+static uint32_t quad_pct4_of(uint32_t p, uint32_t n_units) // (p: GRT_OPT_TILE_PARTS4_PCT)
 {
-    const uint32_t p = (uint32_t)c->opt_tile_parts4_pct;
     return std::min(p, std::max(p / 2u, (uint32_t)((uint64_t)p * n_units / (2u * kTileResidentWaves))));
 }
+static uint32_t quad_pct4(const grt_ctx* c, uint32_t n_units) { return quad_pct4_of((uint32_t)c->opt_tile_parts4_pct, n_units); }
 
 // what a slot's costs, its order and its bundle verdicts belong to: the launch geometry, as six words
 static void launch_geometry_sig(const RenderArgs& a, uint32_t n_units, uint64_t sig[6])
@@ -357,6 +377,7 @@ static int prepare_feedback(grt_ctx* c, RenderArgs& a, hipStream_t s, uint32_t n
         }
         c->cost_cap = n_units;
     }
+    c->sched_units = n_units; // (grt_debug_copy_schedule: the units d_cost and d_order are for, whatever the feedback option)
     if (!c->opt_feedback) { // no scheduling feedback: the cost words are only collected for k_check_costs (tile kernel)
         CHK(c, hipMemsetAsync(c->d_cost, 0, sizeof(uint32_t) * n_units, s));
         a.cost = c->d_cost;
@@ -969,19 +990,8 @@ int grt_render_tiles(grt_ctx* c, const grt_params* p, uint8_t* d_rgb8, float* d_
     RenderArgs a;
     int rc = fill_common(c, p, &a);
     if (rc != GRT_OK) return rc;
-    if (!tile_w || !tile_h || (tile_w % 16) || (tile_h % 16)) { c->err = "grt_render_tiles: tile size must be a multiple of 16"; return GRT_ERR_INVALID; }
-    if (!d_rgb8 && !d_rgbf) { c->err = "grt_render_tiles: no output buffer"; return GRT_ERR_INVALID; }
-    const uint32_t tiles_x = (p->width + tile_w - 1) / tile_w, tiles_y = (p->height + tile_h - 1) / tile_h;
-    if (n_tiles && (!tile_stride || (uint64_t)first_tile + (uint64_t)(n_tiles - 1) * tile_stride >= (uint64_t)tiles_x * tiles_y)) {
-        c->err = "grt_render_tiles: tile range outside the frame's tile grid";
-        return GRT_ERR_INVALID;
-    }
+    if ((rc = set_tiles(c, p, &a, tile_w, tile_h, first_tile, tile_stride, n_tiles, d_rgb8 || d_rgbf, "grt_render_tiles")) != GRT_OK) return rc;
     a.out8 = d_rgb8; a.outf = d_rgbf;
-    a.mode = 1;
-    a.tile_w = tile_w; a.tile_h = tile_h; a.first_tile = first_tile; a.tile_stride = tile_stride; a.n_tiles = n_tiles;
-    a.tiles_x = tiles_x;
-    a.nbx = tile_w / 16; a.nby = tile_h / 16;
-    a.n_blocks = n_tiles * a.nbx * a.nby;
     return do_launch(c, a, stream);
 }
 
@@ -1093,6 +1103,110 @@ int grt_last_kernel_ms(grt_ctx* c, float* ms)
     CHK(c, hipSetDevice(c->device));
     CHK(c, hipEventSynchronize(c->ev1));
     CHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+    return GRT_OK;
+}
+
+// ---- (testing) the launch-order kernels on the caller's arrays, and the slot's schedule as it stands (include/grt.h; tests/order_check.py) ----
+// Never on a render path.  The kernels are reached through the host functions do_launch reaches them by, with the caller's arguments.
+int grt_debug_order_units(grt_ctx* c, grt_debug_order* o)
+{
+    if (!c) return GRT_ERR_INVALID;
+    if (!o) { c->err = "grt_debug_order_units: null arguments"; return GRT_ERR_INVALID; }
+    auto refuse = [&](const char* what) { c->err = std::string("grt_debug_order_units: ") + what; return GRT_ERR_INVALID; };
+    CHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    switch (o->op) {
+    case GRT_DEBUG_ORDER_PARTS: {
+        if (o->n == 0) return refuse("n must be > 0");
+        if (o->n > kOrderUnitMask) return refuse("n does not fit an entry's unit field");
+        if (!o->d_cost || !o->d_cost_raw || !o->d_order) return refuse("null array");
+        if (o->bag_classes > 2u) return refuse("bag_classes must be 0, 1 or 2");
+        const uint32_t cap = o->extra_cap == 0xFFFFFFFFu ? parts_extra_cap(o->n) : o->extra_cap;
+        if ((uint64_t)o->n + cap + 3u > 0xFFFFFFFFull) return refuse("n + extra_cap too large");
+        const uint32_t pct4 = o->quad_pct4 ? quad_pct4_of(o->pct4, o->n) : o->pct4;
+        o->extra_cap_used = cap;
+        o->pct4_used = pct4;
+        return order_units_with_parts(o->d_cost, o->d_cost_raw, o->d_order, o->n, cap, o->pct2, pct4, o->pct_load, o->resident_waves, o->d_zero,
+                                      o->d_scratch, o->multi_min, o->bag_classes, s, &c->err);
+    }
+    case GRT_DEBUG_ORDER_PLAIN:
+        if (o->n == 0) return refuse("n must be > 0");
+        if (!o->d_cost || !o->d_order) return refuse("null array");
+        return order_units_by_cost(o->d_cost, o->d_order, o->n, o->heavy_cap, o->thr_x2, o->d_out, o->d_zero, s, &c->err);
+    case GRT_DEBUG_ORDER_QUAD_LIST:
+        if (o->n == 0) return refuse("n must be > 0");
+        if (!o->d_order || !o->d_out || !o->d_count) return refuse("null array");
+        return quad_part_list(o->d_order, o->n, o->d_out, o->d_count, o->cap, s, &c->err);
+    case GRT_DEBUG_ORDER_DILATE:
+        if (o->nbx == 0 || o->nby == 0 || (uint64_t)o->nbx * o->nby * 4u != o->n) return refuse("n must be nbx x nby x 4 > 0");
+        if (!o->d_cost || !o->d_out || o->d_cost == o->d_out) return refuse("null array, or the output is the input");
+        if (o->radius < 0 || o->radius > 64) return refuse("radius must be 0..64");
+        return dilate_unit_costs(o->d_cost, o->d_out, o->nbx, o->nby, o->radius, s, &c->err);
+    }
+    return refuse("unknown op");
+}
+
+uint32_t grt_debug_order_scratch_bytes(void) { return order_scratch_bytes(); }
+
+int grt_debug_estimate_costs(grt_ctx* c, const grt_params* p, uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                             uint32_t stride, uint32_t* d_cost, uint32_t n_units)
+{
+    if (!c) return GRT_ERR_INVALID;
+    if (!p) { c->err = "grt_debug_estimate_costs: null parameters"; return GRT_ERR_INVALID; }
+    RenderArgs a;
+    int rc = fill_common(c, p, &a);
+    if (rc != GRT_OK) return rc;
+    if (tile_w || tile_h) rc = set_tiles(c, p, &a, tile_w, tile_h, x0, y0, x1, true, "grt_debug_estimate_costs");
+    else rc = set_window(c, p, &a, x0, y0, x1, y1, "grt_debug_estimate_costs");
+    if (rc != GRT_OK) return rc;
+    const grt_ctx* sc = scene_of(c);
+    if (!d_cost) { c->err = "grt_debug_estimate_costs: null array"; return GRT_ERR_INVALID; }
+    if (n_units == 0 || n_units != a.n_blocks * 4u) { c->err = "grt_debug_estimate_costs: n_units is not 4 per 16x16 block of the launch geometry"; return GRT_ERR_INVALID; }
+    if (stride == 0 || sc->n == 0) { c->err = "grt_debug_estimate_costs: stride must be > 0 and a scene uploaded"; return GRT_ERR_INVALID; }
+    CHK(c, hipSetDevice(c->device));
+    const uint32_t ns = ((uint32_t)sc->n + stride - 1) / stride;
+    hipLaunchKernelGGL(k_estimate_costs, dim3((ns + 255) / 256), dim3(256), 0, c->stream, sc->d_pos, (uint32_t)sc->n, stride, a, d_cost);
+    CHK(c, hipGetLastError());
+    return GRT_OK;
+}
+
+int grt_debug_copy_schedule(grt_ctx* c, grt_debug_schedule* o)
+{
+    if (!c) return GRT_ERR_INVALID;
+    if (!o) { c->err = "grt_debug_copy_schedule: null arguments"; return GRT_ERR_INVALID; }
+    CHK(c, hipSetDevice(c->device));
+    if (hipDeviceSynchronize() != hipSuccess) { c->err = "grt_debug_copy_schedule: hipDeviceSynchronize failed"; return GRT_ERR_HIP; }
+    const uint32_t n_units = c->d_cost ? std::min(c->sched_units, c->cost_cap) : 0u;
+    // (an order is for the units of cost_sig's launch geometry; after frames without feedback the arrays may be another geometry's)
+    const bool order = c->order_valid && c->d_order && n_units && (uint32_t)(c->cost_sig[0] >> 8) == n_units;
+    const bool quad = order && c->order_launch && c->qparts_valid && c->d_qparts && c->d_qpcount;
+    uint32_t n_quad = 0;
+    if (quad && hipMemcpy(&n_quad, c->d_qpcount, sizeof(n_quad), hipMemcpyDeviceToHost) != hipSuccess) {
+        c->err = "grt_debug_copy_schedule: copy of the quad list's count failed";
+        return GRT_ERR_HIP;
+    }
+    const uint32_t n_order = !order ? 0u : (c->order_launch ? c->order_launch + 3u : n_units);
+    // (the second call copies what the first one counted: a caller's buffers are sized by those counts)
+    const bool counted = o->n_units == n_units && o->n_order == n_order && o->n_quad == n_quad;
+    o->n_units = n_units;
+    o->order_launch = order ? c->order_launch : 0u;
+    o->order_valid = order ? 1u : 0u;
+    o->order_classes = (order && c->order_launch && c->order_classes) ? 1u : 0u;
+    o->quad_valid = quad ? 1u : 0u;
+    o->n_order = n_order;
+    o->n_quad = n_quad;
+    if (!o->order && !o->quad && !o->cost) return GRT_OK;
+    if (!counted) { c->err = "grt_debug_copy_schedule: the counts have changed since the buffers were sized"; return GRT_ERR_INVALID; }
+    if (n_quad > kQuadListCap) { c->err = "grt_debug_copy_schedule: the quad list's count exceeds its capacity"; return GRT_ERR_LIMIT; }
+    struct Part { void* dst; const void* src; size_t words; };
+    const Part parts[] = {{o->order, c->d_order, n_order}, {o->quad, c->d_qparts, n_quad}, {o->cost, c->d_cost, n_units}};
+    for (const Part& q : parts) {
+        if (!q.dst || !q.words) continue;
+        if (hipMemcpy(q.dst, q.src, q.words * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+            c->err = "grt_debug_copy_schedule: copy of the schedule failed";
+            return GRT_ERR_HIP;
+        }
+    }
     return GRT_OK;
 }
 

@@ -386,6 +386,7 @@ struct grt_ctx {
     int opt_cost_radius = 4; // tiles; 0 = off
     int opt_cold_estimate = 2; // order a frame without previous-frame costs by projected particle counts
     uint32_t cost_cap = 0;
+    uint32_t sched_units = 0; // units of the last launch that went through prepare_feedback with arrays in hand (<= cost_cap)
     bool cost_valid = false;
     bool order_ready = false; // d_order already holds the order for the next frame with this geometry (do_launch, post-frame)
     bool order_split = false;

@@ -47,6 +47,24 @@ class DebugTree(C.Structure):
                [(n, C.c_void_p) for n in ("nodes", "wnodes", "qnodes", "pbox", "order", "rec")]
 
 
+class DebugOrder(C.Structure):
+    """grt_debug_order (include/grt.h): arguments of grt_debug_order_units."""
+    _fields_ = [("op", C.c_uint32), ("n", C.c_uint32)] + \
+               [(n, C.c_void_p) for n in ("d_cost", "d_cost_raw", "d_order", "d_zero", "d_scratch", "d_out", "d_count")] + \
+               [(n, C.c_uint32) for n in ("extra_cap", "pct2", "pct4", "pct_load", "resident_waves", "multi_min", "bag_classes", "quad_pct4",
+                                          "heavy_cap", "thr_x2", "cap", "nbx", "nby")] + \
+               [("radius", C.c_int32), ("extra_cap_used", C.c_uint32), ("pct4_used", C.c_uint32)]
+
+
+class DebugSchedule(C.Structure):
+    """grt_debug_schedule (include/grt.h): what grt_debug_copy_schedule copies."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_units", "order_launch", "order_valid", "order_classes", "quad_valid", "n_order", "n_quad")] + \
+               [(n, C.c_void_p) for n in ("order", "quad", "cost")]
+
+
+DEBUG_ORDER_PARTS, DEBUG_ORDER_PLAIN, DEBUG_ORDER_QUAD_LIST, DEBUG_ORDER_DILATE = 0, 1, 2, 3
+
+
 class MemoryInfo(C.Structure):
     _fields_ = [("scene_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("overflow_pool_bytes", C.c_uint64),
                 ("overflow_chunks", C.c_uint32), ("overflow_demand", C.c_uint32)]
@@ -118,7 +136,8 @@ KERNEL_AUTO, KERNEL_PERLANE, KERNEL_WAVE, KERNEL_STREAM, KERNEL_STREAM_BIG, KERN
 EXPORTS = [
     "grt_create", "grt_create_view", "grt_get_memory_info", "grt_destroy", "grt_last_error", "grt_set_option", "grt_upload_gaussians", "grt_build_bvh",
     "grt_update_gaussians_device",
-    "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
+    "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_debug_order_units",
+    "grt_debug_order_scratch_bytes", "grt_debug_estimate_costs", "grt_debug_copy_schedule", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
     "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
@@ -161,6 +180,11 @@ def lib():
         L.grt_get_bvh_info.argtypes = [vp, C.POINTER(BvhInfo)]
         L.grt_debug_bvh_depth.argtypes = [vp, C.POINTER(u32)]
         L.grt_debug_copy_tree.argtypes = [vp, C.c_int, C.POINTER(DebugTree)]
+        L.grt_debug_order_units.argtypes = [vp, C.POINTER(DebugOrder)]
+        L.grt_debug_order_scratch_bytes.argtypes = []
+        L.grt_debug_order_scratch_bytes.restype = u32
+        L.grt_debug_estimate_costs.argtypes = [vp, C.POINTER(Params), u32, u32, u32, u32, u32, u32, u32, vp, u32]
+        L.grt_debug_copy_schedule.argtypes = [vp, C.POINTER(DebugSchedule)]
         L.grt_render.argtypes = [vp, C.POINTER(Params), vp, vp, u32, u32, u32, u32, vp]
         L.grt_render_tiles.argtypes = [vp, C.POINTER(Params), vp, vp, u32, u32, u32, u32, u32, vp]
         L.grt_assemble_tiles.argtypes = [vp, vp, u32, u32, u32, u32, u32, u32, vp, vp]
@@ -472,6 +496,44 @@ class Tracer:
         for n, a in arr.items():
             setattr(t, n, a.ctypes.data if a.size else None)
         self._check(lib().grt_debug_copy_tree(self._h, which, C.byref(t)))
+        out.update(arr)
+        return out
+
+    def debug_order(self, op, **kw):
+        """(testing) grt_debug_order_units: a launch-order kernel family on the caller's uint32 CUDA tensors (keywords = the fields of
+        grt_debug_order, tensors for the pointers).  The work runs on the context's own stream: the device is synchronised in front of
+        the call and behind it.  Returns the struct (extra_cap_used, pct4_used)."""
+        o = DebugOrder()
+        o.op = op
+        for k, v in kw.items():
+            setattr(o, k, (v.data_ptr() if v is not None else None) if k.startswith("d_") else v)
+        self.sync()
+        rc = lib().grt_debug_order_units(self._h, C.byref(o))
+        self.sync()
+        self._check(rc)
+        return o
+
+    def debug_estimate_costs(self, params, d_cost, stride=1, window=None, tiles=None):
+        """(testing) grt_debug_estimate_costs into the zeroed uint32 CUDA tensor d_cost: window = (x0, y0, x1, y1) (default: the frame)
+        or tiles = (tile_w, tile_h, first, stride, count)."""
+        g = (tiles[0], tiles[1], tiles[2], tiles[3], tiles[4], 0) if tiles else (0, 0) + tuple(window or (0, 0, params.width, params.height))
+        self.sync()
+        rc = lib().grt_debug_estimate_costs(self._h, C.byref(params), *g, stride, d_cost.data_ptr() if d_cost is not None else None,
+                                            d_cost.numel() if d_cost is not None else 0)
+        self.sync()
+        self._check(rc)
+
+    def debug_schedule(self):
+        """(testing) grt_debug_copy_schedule: the slot's scheduling state as a dict — the counts and flags as ints, 'order' (order_launch
+        entries + 3 diagnostic words, or n_units bare entries; empty when no order is held), 'quad' (the quad list), 'cost' (d_cost)
+        as uint32 numpy arrays."""
+        t = DebugSchedule()
+        self._check(lib().grt_debug_copy_schedule(self._h, C.byref(t)))
+        arr = {"order": np.zeros(t.n_order, np.uint32), "quad": np.zeros(t.n_quad, np.uint32), "cost": np.zeros(t.n_units, np.uint32)}
+        for n, a in arr.items():
+            setattr(t, n, a.ctypes.data if a.size else None)
+        self._check(lib().grt_debug_copy_schedule(self._h, C.byref(t)))
+        out = {n: int(getattr(t, n)) for n in ("n_units", "order_launch", "order_valid", "order_classes", "quad_valid", "n_order", "n_quad")}
         out.update(arr)
         return out
 

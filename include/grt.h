@@ -327,6 +327,56 @@ typedef struct {
     float* rec;       /* [n_prims][rec_floats] */
 } grt_debug_tree;
 GRT_API int grt_debug_copy_tree(grt_ctx* ctx, int which, grt_debug_tree* out);
+/* (testing) The launch-order kernels on arrays the CALLER owns (device pointers), through the very host functions a frame calls them
+ * by, for checkers that restate their contract (tests/order_check.py).  Asynchronous on the context's own stream; nothing of the frame
+ * slot's state is read or written.  op selects the function:
+ *   GRT_DEBUG_ORDER_PARTS      order_units_with_parts: d_cost (orders the units), d_cost_raw (their own cost words; may be d_cost itself),
+ *                              n, extra_cap (0xFFFFFFFF: the library's own room for n units), pct2 / pct4 / pct_load, resident_waves,
+ *                              multi_min, bag_classes, d_zero (NULL, or the array to zero: d_cost_raw, which may be d_cost too), d_scratch
+ *                              (NULL, or grt_debug_order_scratch_bytes() of zeroed device memory) -> d_order [n + extra_cap + 3].
+ *                              quad_pct4 != 0: pct4 is taken as GRT_OPT_TILE_PARTS4_PCT and scaled as a quad-parts launch of n units scales it.
+ *                              out: extra_cap_used, pct4_used
+ *   GRT_DEBUG_ORDER_PLAIN      order_units_by_cost: d_cost, n, heavy_cap, thr_x2, d_out (NULL, or one word: the heavy units), d_zero
+ *                              (NULL, or the array to zero) -> d_order [n]
+ *   GRT_DEBUG_ORDER_QUAD_LIST  quad_part_list: d_order [n] (entries, padding included; re-coded in place), cap -> d_out [min(cap, 4096)],
+ *                              d_count [1]
+ *   GRT_DEBUG_ORDER_DILATE     dilate_unit_costs: d_cost [nbx nby 4], nbx, nby, radius -> d_out [nbx nby 4] */
+enum { GRT_DEBUG_ORDER_PARTS = 0, GRT_DEBUG_ORDER_PLAIN = 1, GRT_DEBUG_ORDER_QUAD_LIST = 2, GRT_DEBUG_ORDER_DILATE = 3 };
+typedef struct {
+    uint32_t op, n;
+    const uint32_t* d_cost;
+    const uint32_t* d_cost_raw;
+    uint32_t* d_order;
+    uint32_t* d_zero;
+    uint32_t* d_scratch;
+    uint32_t* d_out;
+    uint32_t* d_count;
+    uint32_t extra_cap, pct2, pct4, pct_load, resident_waves, multi_min, bag_classes, quad_pct4;
+    uint32_t heavy_cap, thr_x2;
+    uint32_t cap;
+    uint32_t nbx, nby;
+    int32_t  radius;
+    uint32_t extra_cap_used, pct4_used; /* out (GRT_DEBUG_ORDER_PARTS) */
+} grt_debug_order;
+GRT_API int grt_debug_order_units(grt_ctx* ctx, grt_debug_order* io);
+GRT_API uint32_t grt_debug_order_scratch_bytes(void);
+/* (testing) The cold frame's estimate (particle centres per 8x8 tile) of the uploaded scene into the caller's zeroed d_cost [n_units],
+ * with the launch geometry of grt_render (tile_w = 0: the window x0, y0, x1, y1) or of grt_render_tiles (tile_w, tile_h, x0 = first
+ * tile, y0 = tile stride, x1 = number of tiles), every stride-th particle.  n_units must be the geometry's: 4 per 16x16 block.
+ * Asynchronous on the context's own stream; the frame slot is not touched. */
+GRT_API int grt_debug_estimate_costs(grt_ctx* ctx, const grt_params* p, uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0,
+                                     uint32_t x1, uint32_t y1, uint32_t stride, uint32_t* d_cost, uint32_t n_units);
+/* (testing) What the frame slot's scheduling state holds right now, copied to host buffers behind a synchronisation of the device.  Two
+ * calls, as grt_debug_copy_tree: with every buffer NULL the counts are filled in; then every non-NULL buffer receives its array.
+ * n_order = order_launch + 3 (the entries and the three diagnostic words) or n_units (bare entries, order_launch = 0), 0 when
+ * order_valid = 0; n_quad = the quad list's count word (0 when quad_valid = 0); cost = the n_units cost words. */
+typedef struct {
+    uint32_t n_units, order_launch, order_valid, order_classes, quad_valid, n_order, n_quad;
+    uint32_t* order; /* [n_order] */
+    uint32_t* quad;  /* [n_quad] */
+    uint32_t* cost;  /* [n_units] */
+} grt_debug_schedule;
+GRT_API int grt_debug_copy_schedule(grt_ctx* ctx, grt_debug_schedule* out);
 
 /* ---- render (all asynchronous on `stream`, a hipStream_t; NULL = the context's own stream) ----
  * d_rgb8 : device uchar3 frame, row-major y*width+x (shaders/tracer.cuh:484-496), may be NULL
