@@ -1242,6 +1242,13 @@ __global__ void k_refit_level(float4* __restrict__ nodes, const uint32_t* __rest
     nodes[(size_t)i * 4 + 2] = make_float4(l1[2], h1[0], h1[1], h1[2]);
 }
 
+// one launch per level of the tree, bottom up, from the boxes of the sorted primitives
+static void refit_levels(DevBvh* bvh, const float4* d_lb_lo, const float4* d_lb_hi, uint32_t grid, int B, hipStream_t stream)
+{
+    for (uint32_t pass = 1; pass <= bvh->height; pass++)
+        hipLaunchKernelGGL(k_refit_level, dim3(grid), dim3(B), 0, stream, bvh->nodes, bvh->level, (int)bvh->n_prims, pass, d_lb_lo, d_lb_hi);
+}
+
 int refit_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, DevBvh* bvh, hipStream_t stream, std::string* err)
 {
     float4 *d_lblo = nullptr, *d_lbhi = nullptr;
@@ -1252,18 +1259,15 @@ int refit_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, DevBvh* bv
         if (err) *err = "refit_lbvh: the BVH was not built with keep_levels";
         return GRT_ERR_INVALID;
     }
+    DevTemps tmp(&d_lblo, &d_lbhi);
     HIPCHK(hipMalloc(&d_lblo, sizeof(float4) * m));
     HIPCHK(hipMalloc(&d_lbhi, sizeof(float4) * m));
     hipLaunchKernelGGL(k_leaf_boxes, dim3((m + B - 1) / B), dim3(B), 0, stream, d_lo, d_hi, bvh->order, m, d_lblo, d_lbhi);
-    for (uint32_t pass = 1; pass <= bvh->height; pass++)
-        hipLaunchKernelGGL(k_refit_level, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, bvh->nodes, bvh->level, (int)m, pass,
-                           d_lblo, d_lbhi);
+    refit_levels(bvh, d_lblo, d_lbhi, (m - 1 + B - 1) / B, B, stream);
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
-    (void)hipFree(d_lblo); (void)hipFree(d_lbhi);
     return GRT_OK;
 fail:
-    (void)hipFree(d_lblo); (void)hipFree(d_lbhi);
     return GRT_ERR_HIP;
 }
 
@@ -1324,11 +1328,31 @@ int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh,
         for (uint32_t pass = 1; pass <= bvh->height; pass++)
             hipLaunchKernelGGL(k_level_pass, dim3(grid), dim3(B), 0, stream, bvh->nodes, bvh->level, (int)m, pass);
     }
-    for (uint32_t pass = 1; pass <= bvh->height; pass++)
-        hipLaunchKernelGGL(k_refit_level, dim3(grid), dim3(B), 0, stream, bvh->nodes, bvh->level, (int)m, pass, d_lb_lo, d_lb_hi);
+    refit_levels(bvh, d_lb_lo, d_lb_hi, grid, B, stream);
     hipLaunchKernelGGL(k_widen, dim3(grid), dim3(B), 0, stream, bvh->nodes, (int)m, bvh->wnodes);
     if (bvh->qnodes) hipLaunchKernelGGL(k_qwiden, dim3(grid), dim3(B), 0, stream, bvh->nodes, (int)m, bvh->qnodes, widen_area_only ? 1 : 0);
     HIPCHK(hipGetLastError());
+    return GRT_OK;
+fail:
+    return GRT_ERR_HIP;
+}
+
+// Launch pass 1, 2, ... of a kernel that gives every node whose children have one a level, until the root (node 0) has one: launch(pass)
+// queues a pass, look(pass) says behind which passes the host reads the root's level back (a 4-byte readback syncs the stream).
+// GRT_ERR_LIMIT when 4096 passes did not get there (the caller has the words for it).
+template <class Launch, class Look>
+static int passes_until_root_has_level(const uint32_t* d_level, hipStream_t stream, std::string* err, Launch launch, Look look, uint32_t* out_level)
+{
+    uint32_t root_level = 0;
+    for (uint32_t pass = 1; root_level == 0; pass++) {
+        if (pass > 4096) return GRT_ERR_LIMIT;
+        launch(pass);
+        if (look(pass)) {
+            HIPCHK(hipMemcpyAsync(&root_level, d_level, 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+    }
+    *out_level = root_level;
     return GRT_OK;
 fail:
     return GRT_ERR_HIP;
@@ -1343,9 +1367,11 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
     uint32_t *d_vals = nullptr, *d_level = nullptr;
     float4 *d_lblo = nullptr, *d_lbhi = nullptr;
     void* d_tmp = nullptr;
+    DevTemps tmp(&d_bounds, &d_keys, &d_keys2, &d_vals, &d_tmp, &d_lblo, &d_lbhi, &d_level, &d_range); // freed on whichever way out
     size_t tmp_bytes = 0;
     uint32_t h_bounds[8];
     uint32_t m = 0;
+    int rc = GRT_OK;
     const int B = 256;
 
     out->n_prims = 0;
@@ -1395,7 +1421,7 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
         HIPCHK(hipStreamSynchronize(stream));
         if (h_bad) {
             if (err) *err = "build_lbvh: internal error: the Morton sort is not sorted / not stable";
-            goto fail_limit;
+            return GRT_ERR_LIMIT;
         }
     }
     m = h_bounds[6];
@@ -1439,28 +1465,14 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
     HIPCHK(hipMalloc(&d_range, sizeof(uint2) * (m - 1)));
     HIPCHK(hipMemsetAsync(d_level, 0, sizeof(uint32_t) * (m - 1), stream));
     hipLaunchKernelGGL(k_hierarchy, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, d_keys2, (int)m, out->nodes, d_range);
-    {
-        uint32_t pass = 0, root_level = 0;
-        while (root_level == 0) {
-            pass++;
-            if (pass > 4096) {
-                if (err) *err = "build_lbvh: refit did not converge";
-                goto fail_limit;
-            }
-            hipLaunchKernelGGL(k_refit_pass, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, out->nodes, d_level,
-                               (int)m, pass, d_lblo, d_lbhi);
-            // poll every few passes only (a 4-byte readback syncs the stream)
-            if (pass >= 8 && (pass & 3) == 0) {
-                HIPCHK(hipMemcpyAsync(&root_level, d_level, 4, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-            } else if (pass < 8 && m <= (1u << pass)) {
-                HIPCHK(hipMemcpyAsync(&root_level, d_level, 4, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-            }
-        }
-        out->height = root_level;
-        out->root_ref = 0;
-    }
+    // (the root is looked at every few passes only: from pass 8 on every fourth; before, once a tree of m leaves can be that shallow)
+    rc = passes_until_root_has_level(
+        d_level, stream, err,
+        [&](uint32_t pass) { hipLaunchKernelGGL(k_refit_pass, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, out->nodes, d_level, (int)m, pass, d_lblo, d_lbhi); },
+        [&](uint32_t pass) { return pass >= 8 ? (pass & 3) == 0 : m <= (1u << pass); }, &out->height);
+    if (rc == GRT_ERR_LIMIT && err) *err = "build_lbvh: refit did not converge";
+    if (rc != GRT_OK) return rc;
+    out->root_ref = 0;
     if (out->wnodes) (void)hipFree(out->wnodes);
     out->wnodes = nullptr;
     HIPCHK(hipMalloc(&out->wnodes, sizeof(float4) * 8 * (size_t)(m - 1) + 256));
@@ -1479,22 +1491,14 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
             for (uint32_t pass = 2; pass <= out->height; pass++)
                 hipLaunchKernelGGL(k_rotate_pass, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, out->nodes, d_level, (int)m, pass, (uint32_t*)nullptr);
             HIPCHK(hipMemsetAsync(d_level, 0, sizeof(uint32_t) * (m - 1), stream));
-            uint32_t pass = 0, root_level = 0;
             const uint32_t h_old = out->height;
-            while (root_level == 0) {
-                pass++;
-                if (pass > 4096) {
-                    if (err) *err = "build_lbvh: levels of the rotated tree did not converge";
-                    goto fail_limit;
-                }
-                hipLaunchKernelGGL(k_level_pass, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, out->nodes, d_level, (int)m, pass);
-                // a sweep changes the height by little: look first where the old height says the root may be done, then every 4 passes
-                if (pass + 2 >= h_old && ((pass + 2 - h_old) & 3u) == 0u) {
-                    HIPCHK(hipMemcpyAsync(&root_level, d_level, 4, hipMemcpyDeviceToHost, stream));
-                    HIPCHK(hipStreamSynchronize(stream));
-                }
-            }
-            out->height = root_level;
+            // a sweep changes the height by little: look first where the old height says the root may be done, then every 4 passes
+            rc = passes_until_root_has_level(
+                d_level, stream, err,
+                [&](uint32_t pass) { hipLaunchKernelGGL(k_level_pass, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, out->nodes, d_level, (int)m, pass); },
+                [&](uint32_t pass) { return pass + 2 >= h_old && ((pass + 2 - h_old) & 3u) == 0u; }, &out->height);
+            if (rc == GRT_ERR_LIMIT && err) *err = "build_lbvh: levels of the rotated tree did not converge";
+            if (rc != GRT_OK) return rc;
         }
     }
     hipLaunchKernelGGL(k_widen, dim3((m - 1 + B - 1) / B), dim3(B), 0, stream, out->nodes, (int)m, out->wnodes);
@@ -1506,16 +1510,8 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
     if (keep_levels) { out->level = d_level; d_level = nullptr; }
 done:
     HIPCHK(hipGetLastError());
-    (void)hipFree(d_bounds); (void)hipFree(d_keys); (void)hipFree(d_keys2); (void)hipFree(d_vals);
-    (void)hipFree(d_tmp); (void)hipFree(d_lblo); (void)hipFree(d_lbhi); (void)hipFree(d_level); (void)hipFree(d_range);
     return GRT_OK;
-fail_limit:
-    (void)hipFree(d_bounds); (void)hipFree(d_keys); (void)hipFree(d_keys2); (void)hipFree(d_vals);
-    (void)hipFree(d_tmp); (void)hipFree(d_lblo); (void)hipFree(d_lbhi); (void)hipFree(d_level); (void)hipFree(d_range);
-    return GRT_ERR_LIMIT;
 fail:
-    (void)hipFree(d_bounds); (void)hipFree(d_keys); (void)hipFree(d_keys2); (void)hipFree(d_vals);
-    (void)hipFree(d_tmp); (void)hipFree(d_lblo); (void)hipFree(d_lbhi); (void)hipFree(d_level); (void)hipFree(d_range);
     return GRT_ERR_HIP;
 }
 

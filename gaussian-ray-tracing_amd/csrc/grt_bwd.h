@@ -191,7 +191,7 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
         const float qw = b.quat[id * 4], qx = b.quat[id * 4 + 1], qy = b.quat[id * 4 + 2], qz = b.quat[id * 4 + 3];
         float Rg[9];
         mat3_cast(qw, qx, qy, qz, Rg);
-        m33 A; // as k_gather_records forms it (grt_api.hip)
+        m33 A; // as k_gather_records forms it (grt_scene.hip)
 #pragma unroll
         for (int r = 0; r < 3; r++) {
 #pragma unroll

@@ -162,7 +162,7 @@ __device__ __forceinline__ bool proxy_sphere_maybe(f3 o_g, f3 d_g, float s)
     return proxy_sphere_maybe_pre(o_g, proxy_sphere_cc(o_g, s), d_g);
 }
 
-// ---- pieces of a split proxy (grt_api.hip: k_piece_boxes) ----
+// ---- pieces of a split proxy (grt_scene.hip: k_piece_boxes) ----
 // The proxy-local box [-tt s, tt s]^3 of Gaussian space (tt = 1.0705: the icosahedron's extent along its principal axes)
 // is cut into p0 x p1 x p2 cells; a piece's descriptor holds its cell (k_r) and the grid (p_r - 1), 5 bits each, bit 31 set.
 constexpr float kIcoTTdev = 1.0704663f;

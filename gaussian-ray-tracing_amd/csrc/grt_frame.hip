@@ -1,6 +1,7 @@
 // grt_frame.hip — the frame slot's unit: what lies between a render entry point of include/grt.h and launch_render (grt_render.hip), and
 // the work queued behind a frame.  The slot's kernels, the arguments every frame shares, the work mappings, the scheduling feedback, the
-// overflow pool, do_launch as a list of stages, the render entry points, the synchronising calls.  Context, options, scene: grt_api.hip.
+// overflow pool, do_launch as a list of stages, the render entry points, the synchronising calls.
+// Context and options: grt_api.hip; the scene: grt_scene.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>

@@ -61,7 +61,7 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
 // Re-fit every reachable node's boxes to new primitive boxes (same primitives, same order, same hierarchy): what a
 // gizmo drag needs (reference: full GAS + IAS rebuild per frame, src/GaussianTracer.cpp:711-794).
 int refit_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, DevBvh* bvh, hipStream_t stream, std::string* err);
-// The Gaussian tree re-fitted to new boxes of its primitives GIVEN IN SORTED ORDER (lb_lo / lb_hi [n_prims]: grt_api.hip k_refit_prim_boxes):
+// The Gaussian tree re-fitted to new boxes of its primitives GIVEN IN SORTED ORDER (lb_lo / lb_hi [n_prims]: grt_scene.hip k_refit_prim_boxes):
 // pbox, the binary nodes level by level (bvh->level is derived from the topology when the build did not keep it, and stays), wnodes, qnodes.
 // Queues its work on the stream and does not wait for it.
 int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh, bool widen_area_only, hipStream_t stream, std::string* err);
@@ -70,6 +70,17 @@ int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh,
 constexpr uint32_t kAreaParts = 256u;
 int lbvh_child_area(const DevBvh* bvh, double* d_part, double* out, hipStream_t stream, std::string* err);
 void free_bvh(DevBvh* b);
+// The device temporaries of one scope: the pointer variables named to the holder are hipFree'd, whatever they hold by then, when it leaves
+// its scope (behind the synchronisation that ends the work on them, as the free lists it replaces were).  A pointer that outlives the
+// scope is handed over and its variable set to nullptr.
+struct DevTemps {
+    void** vars[12]; // (no allocation of its own; the variables are read as void*, as hipMalloc's own template writes them)
+    size_t n;
+    template <class... T> explicit DevTemps(T**... p) : vars{reinterpret_cast<void**>(p)...}, n(sizeof...(T)) {}
+    DevTemps(const DevTemps&) = delete;
+    DevTemps& operator=(const DevTemps&) = delete;
+    ~DevTemps() { for (size_t k = 0; k < n; k++) (void)hipFree(*vars[k]); }
+};
 // exclusive scan of n uint32 values on the device (hand-written, grt_bvh.hip); synchronises the stream
 int device_exclusive_scan_u32(const uint32_t* d_in, uint32_t* d_out, uint32_t n, hipStream_t stream, std::string* err);
 
@@ -77,7 +88,7 @@ int device_exclusive_scan_u32(const uint32_t* d_in, uint32_t* d_out, uint32_t n,
 struct RenderArgs {
     grt_params p;
     // Gaussian scene
-    const float4* rec;    // [n_prox*4] Morton-sorted proxy records (see grt_api.hip: k_gather_records)
+    const float4* rec;    // [n_prox*4] Morton-sorted proxy records (see grt_scene.hip: k_gather_records)
     const float4* erec;   // per-eye part of the proxy test, same order; camera frames only: [n_prox] (grt_frame.hip: k_eye_records) for the
                           // streaming kernel, [n_prox*4] (k_eye_records_wide) for the tile kernel
     const float4* nodes;
@@ -431,7 +442,7 @@ struct grt_ctx {
     bool bwd_pending = false;
     hipStream_t bwd_stream = nullptr;
     int opt_bwd_plain = 0;                  // GRT_OPT_BWD_PLAIN_ATOMICS
-    // device-resident scene update (grt_api.hip: grt_update_gaussians_device)
+    // device-resident scene update (grt_scene.hip: grt_update_gaussians_device)
     int opt_refit_max_area_pct = 200;       // GRT_OPT_REFIT_MAX_AREA_PCT
     int built_opts[5] = {0, 0, 0, 0, 0};    // GRT_OPT_LEAF_MAX, _SIZE_CLASSES, _SPLIT, _SPLIT_VOL_PCT, _BVH_ROTATIONS of the last build
     double area_build = 0.0;                // child half-areas of the tree as BUILT (0 = not measured yet: the first refit measures it)
@@ -457,12 +468,20 @@ struct grt_ctx {
         }                                                                                             \
     } while (0)
 
+// scene calls on a view are refused: the scene belongs to the parent
+#define NOT_A_VIEW(c, what)                                                                           \
+    do {                                                                                              \
+        if ((c)->parent) { (c)->err = what ": this context is a view; change the scene through its parent"; return GRT_ERR_INVALID; } \
+    } while (0)
+
 namespace grt {
 // the context that owns the scene a context renders: itself, or a view's parent
 inline grt_ctx* scene_of(grt_ctx* c) { return c->parent ? c->parent : c; }
 inline const grt_ctx* scene_of(const grt_ctx* c) { return c->parent ? c->parent : c; }
 // grt_frame.hip: everything a frame slot owns (a view has nothing else), freed; for grt_api.hip's grt_create / destroy_now
 void free_slot_state(grt_ctx* c);
+// grt_scene.hip: everything a scene owns (Gaussians, the update's scratch, meshes, both trees, the records), freed; for grt_api.hip's destroy_now
+void free_scene_state(grt_ctx* c);
 // grt_frame.hip: the work mapping of a frame, a backward pass or a statistics pass — a window of the frame (refused when outside it), or a
 // ray buffer (refused when null, or too long).  Each returns GRT_OK or the refusal's code, its text in c->err with the entry point's name `fn` in front.
 int set_window(grt_ctx* c, const grt_params* p, RenderArgs* a, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const char* fn);

@@ -242,7 +242,7 @@ __device__ __forceinline__ void bag_prune(float4* bp, bool doit, uint32_t& nb, u
 // small mesh tree in step on the idle overflow stack) and goes on with the next iteration of the bounce loop.  The same
 // mode finishes the rays of the retry queue (a.single_own_mesh: per-lane segments that went over their budget).
 // Same arithmetic per event, same order: same bits.
-// PIECES = true: the tree holds pieces of split proxies (grt_api.hip: k_piece_boxes) — a piece reports a particle only when
+// PIECES = true: the tree holds pieces of split proxies (grt_scene.hip: k_piece_boxes) — a piece reports a particle only when
 // the lane's first pending event lies in its cell, and the repeats that are still possible are dropped.  Scenes without
 // pieces run the PIECES = false instantiation, whose code is what it was before pieces existed (the few extra
 // instructions cost the default scene 1.3 %, and any change to this kernel's hot loop is a lottery: see the watchdog).
@@ -1117,7 +1117,7 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                 const float hx_ = b1.x - oc.x, hy_ = b1.y - oc.y, hz_ = b1.z - oc.z;
                 // four frustum planes (unit normals n), everything times two: 2 n.centre + min(|n|.extent, 2 radius) is twice the
                 // farthest reach of (box AND bounding sphere) along n.  hi.w = the radius of a sphere about the box centre that
-                // holds the primitive (a proxy's vertices: grt_api.hip k_proxy_boxes; +inf for child boxes and pieces): for a round
+                // holds the primitive (a proxy's vertices: grt_scene.hip k_proxy_boxes; +inf for child boxes and pieces): for a round
                 // proxy the box corner reaches up to sqrt 3 times further along an oblique normal than the proxy does, a third
                 // of the particles a leaf step used to fetch.  The slack covers the rounding of the sums and products:
                 // 2e-5 x the L1 size of the box about the eye

@@ -284,7 +284,7 @@ def _built_asm():
 
 def test_shipped_assembly_has_no_spill_code_in_front_of_an_exec_restore():
     names = {os.path.basename(f) for f in _built_asm()}
-    assert {"grt_render_tile.s", "grt_render_tile_single.s", "grt_render_tile_quad.s", "grt_render_tile_aux.s", "grt_render_stream.s", "grt_render.s", "grt_render_wave.s", "grt_bvh.s", "grt_api.s"} <= names
+    assert {"grt_render_tile.s", "grt_render_tile_single.s", "grt_render_tile_quad.s", "grt_render_tile_aux.s", "grt_render_stream.s", "grt_render.s", "grt_render_wave.s", "grt_bvh.s", "grt_api.s", "grt_scene.s"} <= names
     for f in _built_asm():
         assert V.lint(open(f).read()) == [], os.path.basename(f)
 

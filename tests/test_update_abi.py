@@ -64,7 +64,7 @@ def test_update_kernels_in_the_isa_budget():
     if not os.path.exists(p):
         pytest.fail(f"{p} is missing: build() writes it (profiles/isa_budget_current.py)")
     b = {k["kernel"].split("(")[0]: k for k in json.load(open(p))["kernels"]}
-    want = {"k_refit_prim_boxes": "grt_api.s", "k_regather_records": "grt_api.s", "k_mark_in_tree": "grt_api.s", "k_set_changed": "grt_api.s",
+    want = {"k_refit_prim_boxes": "grt_scene.s", "k_regather_records": "grt_scene.s", "k_mark_in_tree": "grt_scene.s", "k_set_changed": "grt_scene.s",
             "grt::k_child_area_partial": "grt_bvh.s"}
     for name, unit in want.items():
         assert name in b, (name, sorted(k for k in b if "render" not in k))
@@ -72,5 +72,5 @@ def test_update_kernels_in_the_isa_budget():
         # plain streaming kernels: no scratch, no spills
         assert k["file"] == unit and k["scratch_bytes"] == 0 and k["spill_instructions"] == 0, (name, k)
     # the units went through hipcc_via_asm.py unrepaired (its lint ran: build() fails otherwise)
-    for unit in ("grt_api", "grt_bvh"):
+    for unit in ("grt_api", "grt_scene", "grt_bvh"):
         assert int(open(os.path.join(ASM, unit + ".repairs.txt")).readline().split()[0]) == 0
