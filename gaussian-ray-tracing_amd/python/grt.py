@@ -94,6 +94,11 @@ class ParticleStats(C.Structure):
     _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("count", C.c_void_p)]
 
 
+class FeatureGrads(C.Structure):
+    """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
+
+
 class UpdateInfo(C.Structure):
     """grt_update_info (include/grt.h): what grt_update_gaussians_device did."""
     _fields_ = [("mode_used", C.c_uint32), ("reason", C.c_uint32), ("device_ms", C.c_float), ("area_ratio", C.c_float)]
@@ -105,6 +110,8 @@ REASON_NONE, REASON_FIRST_BUILD, REASON_N_CHANGED, REASON_SET_CHANGED, REASON_OP
 
 GRAD_SHAPES = {"pos": (3,), "scale": (3,), "quat": (4,), "opacity": (), "sh": (16, 3)}
 STATS_OUTPUTS = ("weight_sum", "weight_max", "count")
+MAX_FEATURE_CHANNELS = 16  # GRT_MAX_FEATURE_CHANNELS
+FEATURE_GROUPS = ("pos", "scale", "quat", "opacity", "feat")
 
 
 class Mesh(C.Structure):
@@ -139,7 +146,8 @@ EXPORTS = [
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_debug_order_units",
     "grt_debug_order_scratch_bytes", "grt_debug_estimate_costs", "grt_debug_copy_schedule", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
-    "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_sync",
+    "grt_particle_stats_frame", "grt_particle_stats_rays",
+    "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -199,6 +207,10 @@ def lib():
         L.grt_backward_rays_mesh.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_particle_stats_frame.argtypes = [vp, C.POINTER(Params), vp, C.POINTER(ParticleStats), u32, u32, u32, u32, vp]
         L.grt_particle_stats_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(ParticleStats), vp]
+        L.grt_render_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, vp]
+        L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
+        L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
+        L.grt_backward_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, C.POINTER(FeatureGrads), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -724,6 +736,92 @@ class Tracer:
         else:
             x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
             self._check(lib().grt_particle_stats_frame(self._h, C.byref(params), wp, C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return into
+
+    def _feature_inputs(self, what, params, feat, rays, window):
+        """feat [n_particles][C] and rays [n][6] (or None) as contiguous float32 tensors on the tracer's GPU, the shape of the rays'
+        side of the output, and the window."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        feat = t.as_tensor(feat).detach().to(dev, t.float32).contiguous()
+        if feat.dim() != 2 or feat.shape[0] != n or feat.shape[1] < 1:
+            raise GrtError(f"{what}: feat must have shape [{n}][C] with C >= 1, not {tuple(feat.shape)}")
+        if rays is not None:
+            if window is not None:
+                raise GrtError(f"{what}: rays and window exclude each other")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"{what}: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        return feat, rays, shape, (window if window else (0, 0, params.width, params.height)), dev, n
+
+    def render_features(self, params, feat, rays=None, window=None):
+        """grt_render_features_frame / grt_render_features_rays (rays [n][6] given): the caller's per-particle channels feat
+        [n_particles][C] (by original id) composited with the frame's weights, F[ray][c] = sum_i T_i alpha_i feat[id_i][c] over the
+        composited events; include/grt.h.  Returns a float32 tensor [h][w][C] (zero outside the window) or [n][C] on the tracer's
+        GPU.  F is not multiplied by alpha and not normalised.  Any C >= 1: more than 16 channels run in slices of 16."""
+        t = self._torch
+        feat, rays, shape, (x0, y0, x1, y1), dev, n = self._feature_inputs("render_features", params, feat, rays, window)
+        C_ = feat.shape[1]
+        parts = []
+        for c0 in range(0, C_, MAX_FEATURE_CHANNELS):
+            f = feat[:, c0:c0 + MAX_FEATURE_CHANNELS].contiguous()
+            out = t.zeros(shape + (f.shape[1],), dtype=t.float32, device=dev)
+            if n and out.numel():
+                if rays is not None:
+                    self._check(lib().grt_render_features_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
+                                                               out.data_ptr(), self._stream()))
+                else:
+                    self._check(lib().grt_render_features_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], out.data_ptr(), x0, y0, x1, y1,
+                                                                self._stream()))
+            parts.append(out)
+        return parts[0] if len(parts) == 1 else t.cat(parts, -1)
+
+    def backward_features(self, params, feat, grad_out, rays=None, window=None, into=None, groups=None):
+        """grt_backward_features_frame / grt_backward_features_rays: gradients of sum(grad_out * F) for the F of render_features (same
+        params, feat, rays / window; grad_out shaped like F) -> dict of torch tensors over pos, scale, quat, opacity (with respect to
+        the uploaded Gaussians) and feat [n_particles][C], allocated zeroed for `groups` (default: all five), or ACCUMULATED into the
+        tensors of `into` (its keys are the groups computed).  'feat' alone is one traversal and uses no buffer of the tracer.  Any
+        C >= 1: more than 16 channels run in slices of 16 whose gradients add up (the backward is linear in the upstream).  Not
+        bitwise reproducible (float atomics); include/grt.h."""
+        t = self._torch
+        feat, rays, shape, (x0, y0, x1, y1), dev, n = self._feature_inputs("backward_features", params, feat, rays, window)
+        C_ = feat.shape[1]
+        grad_out = t.as_tensor(grad_out).detach().to(dev, t.float32).contiguous()
+        if tuple(grad_out.shape) != shape + (C_,):
+            raise GrtError(f"backward_features: grad_out must have shape {shape + (C_,)}, not {tuple(grad_out.shape)}")
+        shapes = {k: ((C_,) if k == "feat" else GRAD_SHAPES[k]) for k in FEATURE_GROUPS}
+        if into is None:
+            bad = [k for k in (groups if groups is not None else ()) if k not in FEATURE_GROUPS]
+            if bad or (groups is not None and not len(groups)):
+                raise GrtError(f"backward_features: groups must be a non-empty subset of {FEATURE_GROUPS}, not {tuple(groups)}")
+            into = {k: t.zeros((n,) + shapes[k], dtype=t.float32, device=dev) for k in (groups if groups is not None else FEATURE_GROUPS)}
+        for k, v in into.items():
+            if k not in FEATURE_GROUPS or tuple(v.shape) != (n,) + shapes[k] or v.dtype != t.float32 or not v.is_contiguous() or v.device != dev:
+                raise GrtError(f"backward_features: gradient tensor '{k}' must be contiguous float32 of shape {(n,) + shapes[k]} on {dev}")
+        if not into:
+            raise GrtError("backward_features: no gradient group asked for")
+        if not n or not grad_out.numel():
+            return into
+        sliced = C_ > MAX_FEATURE_CHANNELS
+        for c0 in range(0, C_, MAX_FEATURE_CHANNELS):
+            f = feat[:, c0:c0 + MAX_FEATURE_CHANNELS].contiguous()
+            g = grad_out[..., c0:c0 + MAX_FEATURE_CHANNELS].contiguous()
+            gf = None
+            if "feat" in into:  # (a slice of the [n][C] tensor is not contiguous: its gradient goes through a tensor of its own)
+                gf = t.zeros_like(f) if sliced else into["feat"]
+            ptrs = FeatureGrads(*(into[k].data_ptr() if k in into else None for k in FEATURE_GROUPS[:4]), gf.data_ptr() if gf is not None else None)
+            if rays is not None:
+                self._check(lib().grt_backward_features_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
+                                                             g.data_ptr(), C.byref(ptrs), self._stream()))
+            else:
+                self._check(lib().grt_backward_features_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], g.data_ptr(), C.byref(ptrs),
+                                                              x0, y0, x1, y1, self._stream()))
+            if gf is not None and sliced:
+                into["feat"][:, c0:c0 + MAX_FEATURE_CHANNELS] += gf
         return into
 
     def _ex_buffers(self, into, groups, dev, ray_shape):

@@ -17,6 +17,11 @@ A `rays` tensor that requires grad receives its gradient ([n][6]: dloss/do, dlos
 `camera=`; when none of the Gaussian leaves requires grad the backward runs the rays-only kernel (no atomics, no gradient buffer).
 The backward differentiates the scene the tracer HOLDS: it must run before the next upload to the same tracer (another
 grt_torch.render included), and raises GrtError otherwise.  This is the only module of the package that imports torch at load.
+
+    F = grt_torch.render_features(tracer, params, feat, geometry=(pos, scale, quat, opacity))          # [h][w][C] of feat [n][C]
+
+composites the caller's own per-particle channels with the weights of the scene the tracer holds, differentiable
+with respect to feat and to the four geometry tensors of the last upload; it uploads nothing, so it shares a backward with render().
 """
 import numpy as np
 import torch
@@ -146,3 +151,59 @@ def particle_stats(tracer, params, rays=None, ray_weight=None, into=None):
     differentiable: the tensors carry no graph."""
     with torch.no_grad():
         return tracer.particle_stats(params, rays=rays, ray_weight=ray_weight, into=into)
+
+
+class _RenderFeatures(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, pos, scale, quat, opacity, rays, tracer, params):
+        # pos .. opacity: the tensors of the tracer's last upload (or None): only the carriers of the geometry gradients
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.params = tracer, params
+        ctx.rays = rays.detach() if rays is not None else None
+        ctx.like = tuple((t.device, t.dtype) if t is not None else None for t in (feat, pos, scale, quat, opacity))
+        ctx.save_for_backward(feat.detach())
+        return tracer.render_features(params, feat.detach(), rays=ctx.rays)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        (feat,) = ctx.saved_tensors
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("feat", "pos", "scale", "quat", "opacity")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:5]) if want]
+        if not groups:
+            return (None,) * 8
+        g = tr.backward_features(ctx.params, feat, g_out, rays=ctx.rays, groups=groups)
+        return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 3
+
+
+def render_features(tracer, params, feat, rays=None, geometry=None):
+    """F [h][w][C] (or [n][C] for `rays` [n][6]) of the per-particle channels feat [n_particles][C] composited with the frame's
+    weights T_i alpha_i (Tracer.render_features; include/grt.h: grt_render_features_frame / _rays), differentiable with respect to
+    feat and, with geometry=(pos, scale, quat, opacity), with respect to those four as well.  Any C >= 1.
+    It renders the scene the tracer HOLDS and uploads nothing, like particle_stats: grt_torch.render(tracer, ...) followed by
+    grt_torch.render_features(tracer, ...) can share one loss.backward().  The `geometry` tensors only carry the gradient — they
+    must be the tensors of the tracer's last upload (the ones given to grt_torch.render), their shapes are checked against the
+    tracer's particle count and their values are not read.  The backward raises GrtError when the tracer has received another upload
+    since the forward.  Gradients with respect to rays are not computed (`rays` that requires grad: ValueError), and neither are
+    mesh frames (a tracer with meshes: ValueError)."""
+    if tracer.has_meshes:
+        raise ValueError("grt_torch.render_features: meshes are set on this tracer; feature channels are rendered for Gaussian-only frames")
+    if rays is not None and rays.requires_grad:
+        raise ValueError("grt_torch.render_features: gradients with respect to rays are not computed through features; detach rays")
+    geo = (None,) * 4
+    if geometry is not None:
+        geo = tuple(geometry)
+        scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene)
+        n = scene.n_particles
+        want = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,)}
+        if len(geo) != 4 or any(not torch.is_tensor(t) for t in geo):
+            raise ValueError("grt_torch.render_features: geometry must be four tensors (pos, scale, quat, opacity)")
+        for (name, shape), t in zip(want.items(), geo):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"grt_torch.render_features: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
+                                 f"not {tuple(t.shape)}")
+    return _RenderFeatures.apply(feat, *geo, rays, tracer, params)

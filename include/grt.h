@@ -597,6 +597,61 @@ GRT_API int grt_particle_stats_frame(grt_ctx* ctx, const grt_params* p, const fl
                                      const grt_particle_stats* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_particle_stats_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n,
                                     const float* d_ray_weight /* may be NULL */, const grt_particle_stats* out, void* stream);
+/* ---- per-particle feature channels rendered through the Gaussians, with gradients (Gaussian-only frames) ----
+ * The caller's own per-particle quantity — semantic or language embeddings, labels, an error or an age for a heat map, any learned
+ * channel — composited with the renderer's weights, and the gradient back to it and to the Gaussians: feature-field distillation on
+ * frozen geometry, or joint training of colour and features on one scene.  A COMPOSITED EVENT is exactly the backward pass's and the
+ * statistics' (above): the k-buffer's events i in key order, BOTH the entry and the exit event of a proxy, repeats of a split
+ * particle's pieces dropped, an event counted when alpha_min < alpha_i, the walk going on while T > minTransmittance and the last
+ * distance <= t_max; the same rays are skipped (fisheye r > 1, |d| <= 0.1, a NaN direction, max_bounces = 0, an empty tree).
+ *   feat       [n][C] float32 on the device, by ORIGINAL particle id, owned by the caller and passed per call like a ray buffer: the
+ *              context keeps nothing of it.
+ *   channels   C, 1 .. GRT_MAX_FEATURE_CHANNELS (more channels: several calls over slices of 16).
+ * FORWARD, over the composited events i of a ray in compositing order:
+ *     F[ray][c] = sum_i w_i feat[id_i][c],     w_i = T_i alpha_i,     T_1 = 1, T_{i+1} = T_i (1 - alpha_i)
+ * T_i the transmittance BEFORE the event, w_i ONE float32 product of the forward's own two factors (as for the statistics), each term
+ * added as F_c = F_c + w_i * f_c in float32 without contraction.  F is NOT multiplied by the frame's alpha and is not normalised: with
+ * feat = 1 it is sum w_i = 1 - T_end up to rounding (grt_aux_out::alpha before its clamp).  Every element of the window
+ * ([h][w][C], laid out like the frame) or of the buffer ([n][C]) is WRITTEN once — zeros for a ray that is not traced; pixels outside
+ * the window are untouched.  No atomic is in its path: the forward is bitwise reproducible, and windows tile a frame bit for bit.
+ * BACKWARD of loss = sum_ray sum_c g[ray][c] F[ray][c], every discrete decision held fixed as in grt_backward.  Per ray, with
+ *     phi_i = sum_c g_c feat[id_i][c],     Phi = sum_i w_i phi_i,     P_i = sum_{j<=i} w_j phi_j      (formed in compositing order)
+ *     dloss/dalpha_i        = T_i phi_i - (Phi - P_i) / (1 - alpha_i)
+ *     dloss/dfeat[j][c]    += sum over the composited events i of particle j of  w_i g[ray][c]
+ * dloss/dalpha_i is grt_backward's with the one-channel radiance L = (phi_i, 0, 0), g_rad = (1, 0, 0), S = (Phi - P_i, 0, 0) and
+ * g_A' = 0; below alpha_i the chain to pos, scale, quat and opacity is grt_backward's own — nothing where the 0.99 clamp binds, the
+ * quaternion AS UPLOADED.  A ray whose C upstream values are all exactly 0 is not traced.  All gradients are ADDED into the caller's
+ * arrays ([n][3] [n][3] [n][4] [n] and [n][C], by original id; the caller zeroes them); any subset of the five may be NULL, all five
+ * NULL: GRT_ERR_INVALID.  With pos, scale, quat and opacity all NULL the call is ONE traversal and touches no buffer of the context;
+ * otherwise two (Phi comes from a first sweep: the forward's F is not an argument), through the context's 64-B-per-particle gradient
+ * buffer and its flush exactly as grt_backward (created by the first such call; the higher-SH buffer never is).  Float atomics: not
+ * bitwise reproducible between calls; GRT_OPT_BWD_PLAIN_ATOMICS = 1 makes every lane issue its own (testing).
+ * The forward uses no buffer of the context (grt_memory_info::slot_bytes is unchanged by it); a frame rendered after either call is
+ * bit-identical to one rendered before it; a view computes its scene's result.  Asynchronous on `stream` like grt_render;
+ * grt_last_kernel_ms reports the call's device time.  With no rays, no particles or an empty tree the calls return GRT_OK: the
+ * forward writes zeros, the backward nothing.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): everything
+ * grt_backward refuses (NULL p, no BVH, GRT_OPT_COUNTERS = 1, sh_degree_max > 3, t_min <= 0, a window outside the frame, a NULL ray
+ * buffer), meshes set (feature channels are rendered for Gaussian-only frames), channels 0 or above GRT_MAX_FEATURE_CHANNELS, a NULL
+ * feat, output or upstream.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB, as in the backward.
+ * Not computed: gradients with respect to rays or the camera through features, an alpha / depth / normalised output (grt_render_aux
+ * has alpha), mesh frames. */
+#define GRT_MAX_FEATURE_CHANNELS 16
+typedef struct {
+    float* pos;
+    float* scale;
+    float* quat;
+    float* opacity;
+    float* feat; /* [n][channels] */
+} grt_feature_grads;
+GRT_API int grt_render_features_frame(grt_ctx* ctx, const grt_params* p, const float* d_feat, uint32_t channels, float* d_out, uint32_t x0,
+                                      uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_render_features_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_feat,
+                                     uint32_t channels, float* d_out, void* stream);
+GRT_API int grt_backward_features_frame(grt_ctx* ctx, const grt_params* p, const float* d_feat, uint32_t channels, const float* d_grad_out,
+                                        const grt_feature_grads* grads, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_features_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_feat,
+                                       uint32_t channels, const float* d_grad_out, const grt_feature_grads* grads, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
