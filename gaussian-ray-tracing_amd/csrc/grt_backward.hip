@@ -3,7 +3,8 @@
 //
 // The device text is grt_bwd.h; this unit instantiates k_backward<MERGE> from it and holds what exists once for the three backward
 // units: the flush kernels, the context's gradient buffers, and the host path every entry point takes (grt_internal.h: bwd_fill_args,
-// bwd_launch; the work mappings set_window and set_rays are grt_frame.hip's).
+// bwd_launch; the work mappings set_window and set_rays are grt_frame.hip's) — and, for grt_stats.hip and grt_features.hip as well,
+// the launch of a one-ray-per-lane kernel (lane_launch, lane_launch_done).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -85,9 +86,8 @@ static int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* 
         const uint64_t nh = n * kShHi;
         hipLaunchKernelGGL(k_bwd_flush_sh, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, c->d_gacc_sh, nh, g->sh);
     }
-    CHK(c, hipGetLastError());
-    CHK(c, hipEventRecord(c->ev1, s));
-    c->have_timing = true;
+    int rc = lane_launch_done(c, s);
+    if (rc != GRT_OK) return rc;
     if (!c->ev_bwd) CHK(c, hipEventCreateWithFlags(&c->ev_bwd, hipEventDisableTiming));
     CHK(c, hipEventRecord(c->ev_bwd, s));
     c->bwd_pending = true; c->bwd_stream = s;
@@ -96,13 +96,13 @@ static int bwd_flush(grt_ctx* c, uint64_t n, bool hi, const grt_gaussian_grads* 
 
 namespace grt {
 
-int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn)
+int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn, const char* gauss_only)
 {
     if (!c) return GRT_ERR_INVALID;
     if (!p) { c->err = std::string(fn) + ": null parameters"; return GRT_ERR_INVALID; }
     const grt_ctx* sc = scene_of(c);
     if (!sc->built) { c->err = std::string(fn) + ": grt_build_bvh has not been called after the last upload"; return GRT_ERR_INVALID; }
-    if (!mesh && sc->n_faces) { c->err = std::string(fn) + ": meshes are set (grt_backward_mesh / grt_backward_rays_mesh differentiate mesh frames)"; return GRT_ERR_INVALID; }
+    if (!mesh && sc->n_faces) { c->err = std::string(fn) + ": meshes are set (" + gauss_only + ")"; return GRT_ERR_INVALID; }
     if (c->opt_counters) { c->err = std::string(fn) + ": GRT_OPT_COUNTERS = 1 (the backward kernel is not instrumented)"; return GRT_ERR_INVALID; }
     if (p->sh_degree_max > 3) { c->err = std::string(fn) + ": sh_degree_max must be 0..3"; return GRT_ERR_INVALID; }
     if (mesh && (p->type < 0 || p->type > 2)) { c->err = std::string(fn) + ": type must be MIRROR/NORMAL/GLASS"; return GRT_ERR_INVALID; }
@@ -130,16 +130,38 @@ int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, con
     return GRT_OK;
 }
 
+int lane_launch(grt_ctx* c, const RenderArgs& a, const void* kernel, void** args, hipStream_t s, const char* fn)
+{
+    const grt_ctx* sc = scene_of(c);
+    // one LDS stack per lane, for the Gaussian tree and, in a frame with meshes, for the mesh tree in turn
+    // (no particle or an empty tree: depth 1; the kernels' guard makes every ray untraced and the stack is not touched)
+    const uint32_t depth = std::max(std::max(sc->gbvh.height, a.n_faces ? sc->mbvh.height : 0u), 1u);
+    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
+    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
+    CHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CHK(c, hipEventRecord(c->ev0, s));
+    (void)hipLaunchKernel(kernel, dim3(a.n_blocks), dim3(kBlock), args, lds, s); // (a failed launch: hipGetLastError in lane_launch_done)
+    return GRT_OK;
+}
+
+int lane_launch_done(grt_ctx* c, hipStream_t s)
+{
+    CHK(c, hipGetLastError());
+    CHK(c, hipEventRecord(c->ev1, s));
+    c->have_timing = true;
+    return GRT_OK;
+}
+
 int bwd_launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha,
-               const grt_gaussian_grads* g, float* d_ray_grads, const void* const kernels[3], void* stream, const char* fn)
+               const grt_gaussian_grads* g, const BwdUnit& u, void* stream, const char* fn)
 {
     const grt_ctx* sc = scene_of(c);
     const uint64_t n = sc->n;
     const bool want_geom = g && (g->pos || g->scale || g->quat || g->opacity);
     const bool want_sh = g && g->sh;
     const bool gauss = (want_geom || want_sh) && n != 0 && sc->gbvh.root_ref != kNoRoot;
-    // no ray, or nothing to differentiate (with a per-ray output an empty scene or an empty tree still runs: the rays-only kernel writes the zeros)
-    if (a.n_blocks == 0 || (!gauss && !d_ray_grads)) { c->have_timing = false; return GRT_OK; }
+    // no ray, or nothing to differentiate (a unit with work of its own still runs on an empty scene or an empty tree: the rays-only kernel writes the zeros)
+    if (a.n_blocks == 0 || (!gauss && !u.own_work)) { c->have_timing = false; return GRT_OK; }
     CHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool hi = gauss && p->sh_degree_max > 0 && want_sh;
@@ -147,29 +169,16 @@ int bwd_launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float
         int rc = bwd_buffers(c, n, hi, s);
         if (rc != GRT_OK) return rc;
     }
-    // one LDS stack per lane, for the Gaussian tree and, in a frame with meshes, for the mesh tree in turn
-    const uint32_t depth = std::max(std::max(sc->gbvh.height, a.n_faces ? sc->mbvh.height : 0u), 1u);
-    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth;
-    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
     BwdArgs b;
     b.pos = sc->d_pos; b.scale = sc->d_scale; b.quat = sc->d_quat; b.opacity = sc->d_opacity;
     b.g_rgb = d_grad_rgbf; b.g_alpha = d_grad_alpha;
     b.acc = gauss ? c->d_gacc : nullptr; b.acc_sh = hi ? c->d_gacc_sh : nullptr;
-    b.want_geom = (want_geom || d_ray_grads) ? 1u : 0u; // (the rays need m = A^T g_p of every event)
+    b.want_geom = (want_geom || u.own_work) ? 1u : 0u; // (own work: the rays need m = A^T g_p of every event)
     b.want_sh = (gauss && want_sh) ? 1u : 0u;
-    RayOut ro;
-    ro.rays = d_ray_grads;
-    ro.scatter_geom = (gauss && want_geom) ? 1u : 0u;
-    const void* fnk = kernels[!gauss ? 0 : (c->opt_bwd_plain ? 1 : 2)];
-    CHK(c, hipFuncSetAttribute(fnk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CHK(c, hipEventRecord(c->ev0, s));
-    void* args[3] = {const_cast<RenderArgs*>(&a), &b, &ro}; // (a kernel without a per-ray output takes the first two)
-    (void)hipLaunchKernel(fnk, dim3(a.n_blocks), dim3(kBlock), args, lds, s); // (a failed launch: hipGetLastError below / in bwd_flush)
-    if (gauss) return bwd_flush(c, n, hi, g, s);
-    CHK(c, hipGetLastError());
-    CHK(c, hipEventRecord(c->ev1, s));
-    c->have_timing = true;
-    return GRT_OK;
+    void* args[3] = {const_cast<RenderArgs*>(&a), &b, u.arg}; // (a kernel without an argument of its unit's takes the first two)
+    int rc = lane_launch(c, a, u.kernels[!gauss ? 0 : (c->opt_bwd_plain ? 1 : 2)], args, s, fn);
+    if (rc != GRT_OK) return rc;
+    return gauss ? bwd_flush(c, n, hi, g, s) : lane_launch_done(c, s);
 }
 
 } // namespace grt
@@ -179,7 +188,7 @@ static int launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const fl
 {
     if (!d_rgbf || !d_alpha || !d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_rgbf, d_alpha, d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
     static const void* const kernels[3] = {nullptr, reinterpret_cast<const void*>(k_backward<false>), reinterpret_cast<const void*>(k_backward<true>)};
-    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, nullptr, kernels, stream, fn);
+    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, BwdUnit{kernels, nullptr, false}, stream, fn);
 }
 
 extern "C" {

@@ -208,7 +208,7 @@ static int launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const fl
 {
     if (!d_grad_rgbf || !g) { c->err = std::string(fn) + ": null pointer (d_grad_rgbf and the grads structure are required)"; return GRT_ERR_INVALID; }
     static const void* const kernels[3] = {nullptr, reinterpret_cast<const void*>(k_backward_mesh<false>), reinterpret_cast<const void*>(k_backward_mesh<true>)};
-    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, nullptr, kernels, stream, fn);
+    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, BwdUnit{kernels, nullptr, false}, stream, fn);
 }
 
 extern "C" {

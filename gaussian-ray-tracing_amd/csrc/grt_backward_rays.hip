@@ -28,7 +28,11 @@ static int launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const fl
     if (!d_rgbf || !d_alpha || !d_grad_rgbf) { c->err = std::string(fn) + ": null pointer (d_rgbf, d_alpha and d_grad_rgbf are required)"; return GRT_ERR_INVALID; }
     static const void* const kernels[3] = {reinterpret_cast<const void*>(k_backward_rays<false, false>), reinterpret_cast<const void*>(k_backward_rays<false, true>),
                                            reinterpret_cast<const void*>(k_backward_rays<true, true>)};
-    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, out->gaussians, out->rays, kernels, stream, fn);
+    const grt_gaussian_grads* g = out->gaussians;
+    RayOut ro;
+    ro.rays = out->rays;
+    ro.scatter_geom = (g && (g->pos || g->scale || g->quat || g->opacity)) ? 1u : 0u; // (read by the GAUSS = true kernels alone)
+    return bwd_launch(c, p, a, d_grad_rgbf, d_grad_alpha, g, BwdUnit{kernels, &ro, true}, stream, fn);
 }
 
 extern "C" {

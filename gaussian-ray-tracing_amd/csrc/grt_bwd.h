@@ -1,6 +1,9 @@
-// grt_bwd.h — the device text the three backward units share (grt_backward.hip, grt_backward_rays.hip, grt_backward_mesh.hip;
-// DESIGN.md 5.8, 5.10, 5.11): the kernels' arguments, the terms of one composited event, the scatter into the gradient buffer, a
-// lane's ray and upstream gradient, and the ONE body of k_backward<MERGE> and k_backward_rays<MERGE, GAUSS>.
+// grt_bwd.h — the device text the units that walk a ray's composited events share (grt_backward.hip, grt_backward_rays.hip,
+// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip): the kernels' arguments, a
+// lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics and
+// the feature kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
+// grouping of a wave's lanes by particle (wave_groups), the terms of one composited event, the scatter into the gradient buffer, and
+// the ONE body of k_backward<MERGE> and k_backward_rays<MERGE, GAUSS>.
 //
 // One ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round (grt_kround.h: the round trace_gaussians of grt_render.hip
 // runs, without its watchdog and counters), twice per ray:
@@ -116,6 +119,32 @@ __device__ __forceinline__ void scatter_own(float* __restrict__ acc, uint32_t id
     }
 }
 
+// The wave merge, called by the WHOLE wave (ev: this lane has an event of particle id).  The lanes with an event are grouped by id
+// (the lowest lane left leads, v_readlane hands its id round, a ballot finds its group); for every group of two or more lanes the
+// whole wave calls on_group(id, mine, n, leader) — the group's id, whether this lane belongs to it, its size and its leader's lane —
+// so on_group may hold wave operations.  Returns whether this lane is alone with its id: its own adds are the caller's, once the
+// groups are done.  The loop is wave-uniform: todo is a ballot.
+template <class OnGroup>
+__device__ __forceinline__ bool wave_groups(bool ev, uint32_t id, OnGroup&& on_group)
+{
+    uint64_t todo = __builtin_amdgcn_ballot_w64(ev);
+    bool solo = false;
+    while (todo) {
+        const int leader = __builtin_ctzll(todo);
+        const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, leader);
+        const bool mine = ev && id == lid;
+        const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
+        todo &= ~m;
+        const uint32_t n = (uint32_t)__builtin_popcountll(m);
+        if (n == 1u) {
+            solo = solo || mine;
+            continue;
+        }
+        on_group(lid, mine, n, (uint32_t)leader);
+    }
+    return solo;
+}
+
 // Called by the WHOLE wave (ev: this lane has an event).  MERGE: lanes with the same particle add once.
 template <bool MERGE>
 __device__ __forceinline__ void scatter(float* __restrict__ acc, bool ev, uint32_t id, const float v[kVals], bool geom, bool colour, uint32_t lane)
@@ -124,18 +153,7 @@ __device__ __forceinline__ void scatter(float* __restrict__ acc, bool ev, uint32
         if (ev) scatter_own(acc, id, v, geom, colour);
         return;
     }
-    uint64_t todo = __builtin_amdgcn_ballot_w64(ev);
-    bool solo = false;
-    while (todo) { // wave-uniform
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, leader);
-        const bool mine = ev && id == lid;
-        const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
-        todo &= ~m;
-        if (__builtin_popcountll(m) == 1) { // alone with its particle: its own adds, once the groups are done
-            solo = solo || mine;
-            continue;
-        }
+    const bool solo = wave_groups(ev, id, [&](uint32_t lid, bool mine, uint32_t, uint32_t) {
         float out = 0.0f;
 #pragma unroll
         for (int k = 0; k < kVals; k++) {
@@ -143,7 +161,7 @@ __device__ __forceinline__ void scatter(float* __restrict__ acc, bool ev, uint32
             out = (lane == (uint32_t)k) ? s : out;
         }
         if (lane < (uint32_t)kVals && out != 0.0f) atomicAdd(acc + (size_t)lid * kRow + lane, out);
-    }
+    });
     if (solo) scatter_own(acc, id, v, geom, colour);
 }
 
@@ -288,6 +306,65 @@ __device__ __forceinline__ bool load_upstream(const BwdArgs& b, size_t idx, bool
         live = (gC.x != 0.0f) || (gC.y != 0.0f) || (gC.z != 0.0f) || (gA != 0.0f);
     }
     return live;
+}
+
+// The ONE sweep over the events trace() composites on a ray segment (shaders/tracer.cuh:328-373): rounds of gps_round through its
+// single call site until the segment [t_min, t_max] or the transmittance runs out, and per round the K slots of the k-buffer in
+// order — the forward's events in the forward's order.  stk: the lane's LDS stack; part: this lane takes part at all; T: the
+// transmittance, carried in and out (1, or what the ray's earlier segments left).  For every slot of every round the WHOLE wave calls
+// on_slot(ev, id, Tb, hitAlpha) once: ev — this lane composites an event in the slot, of particle id with alpha hitAlpha, at
+// transmittance Tb before it (ev false: id 0, nothing to use); T *= 1 - hitAlpha follows the call.
+//
+// Wave convergence: on_slot may hold wave operations (scatter<MERGE>: DPP, v_readlane), so every lane of the wave reaches it for
+// every slot of every round.  The round loop is entered and left on a ballot over the lanes' own `act`, the slot loop has a constant
+// trip count, and a lane whose own condition is false idles inside them with `act` cleared.  The round itself is the per-lane
+// gps_round inside `if (act)`, with no wave operation in it.  A lane's rounds are bounded by lastT rising past the segment's end:
+// the ballot becomes zero.  A caller that loops around the sweep (passes) enters and leaves its loops the same way.
+// backward_body and k_backward_mesh hold this loop written out, statement for statement: a change here is a change there.
+template <class OnSlot>
+__device__ __forceinline__ void sweep_events(const RenderArgs& a, uint32_t* stk, f3 o, f3 d, const rayinv& ri, float t_max, bool part, float& T,
+                                             OnSlot&& on_slot)
+{
+    const float epsT = 1e-9f;
+    const float t_hi = t_max + epsT;
+    const float minT = a.p.minTransmittance;
+    const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
+    KBuf<K> kb;
+    grt::Cnt cnt; // (dead: no counters, no watchdog; grt::Cnt is the round's, grt_kround.h — Cnt alone would be grt_wave.h's)
+    float lastT = a.p.t_min;
+    uint64_t last_key = key0;
+    bool act = part && (lastT <= t_max) && (T > minT);
+    while (__builtin_amdgcn_ballot_w64(act)) {
+        if (act) {
+            gps_round<false, false, K>(a, stk, o, d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
+            if (kb.key[0] == kKeyInvalid) act = false;
+        }
+#pragma unroll 1
+        for (int i = 0; i < K; i++) {
+            bool ev = false;
+            uint32_t id = 0;
+            uint64_t key = kKeyInvalid;
+            float hitAlpha = 0.0f;
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                if (j == i) { key = kb.key[j]; hitAlpha = kb.alpha[j]; }
+            }
+            if (act && key != kKeyInvalid && T > minT) {
+                lastT = fmaxf(key_t(key), lastT);
+                if (a.p.alpha_min < hitAlpha) {
+                    ev = true;
+                    id = key_id(key);
+                }
+            }
+            on_slot(ev, id, T, hitAlpha);
+            if (ev) T *= (1.0f - hitAlpha);
+        }
+        if (act) {
+            if (kb.key[K - 1] == kKeyInvalid) act = false;
+            else last_key = kb.key[K - 1];
+            act = act && (lastT <= t_max) && (T > minT);
+        }
+    }
 }
 
 // The body of k_backward<MERGE> (GAUSS = true, RAYS = false; ro unused) and of k_backward_rays<MERGE, GAUSS> (RAYS = true: every

@@ -489,11 +489,25 @@ int set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const c
 // grt_backward.hip: the host path of the backward entry points (grt_backward*.hip).  Each returns GRT_OK or the refusal's code, its
 // text in c->err with the entry point's name `fn` in front.
 // The arguments every backward kernel reads, after the refusals all entry points share (null p, no BVH, counters on, sh_degree_max,
-// t_min).  mesh: the mesh side is filled and p->type checked; without it a scene with meshes is refused.
-int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn);
-// The launch: gradient buffers, LDS stack, the kernel between ev0 and ev1, the flush.  kernels: the calling unit's instantiations —
-// [0] the one that scatters nothing (runs when there is a per-ray output d_ray_grads and no Gaussian gradient to form; else null),
-// [1] plain atomics, [2] the wave merge — each taking (RenderArgs, BwdArgs) or (RenderArgs, BwdArgs, RayOut) of grt_bwd.h.
+// t_min).  mesh: the mesh side is filled and p->type checked; without it a scene with meshes is refused, with `gauss_only` in the
+// refusal's parenthesis (a unit without a mesh variant says so in its own words).
+int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn,
+                  const char* gauss_only = "grt_backward_mesh / grt_backward_rays_mesh differentiate mesh frames");
+// The launch of a one-ray-per-lane kernel over a.n_blocks blocks (grt_bwd.h, kRoundBlock lanes each): one LDS stack per lane as deep
+// as the Gaussian tree and, where a.n_faces, the mesh tree (more than 160 KiB: GRT_ERR_LIMIT), ev0, the kernel with `args` on s.
+// lane_launch_done: the launch's error, ev1 and have_timing behind it — or behind what the caller put on s in between.
+int lane_launch(grt_ctx* c, const RenderArgs& a, const void* kernel, void** args, hipStream_t s, const char* fn);
+int lane_launch_done(grt_ctx* c, hipStream_t s);
+// What a unit hands bwd_launch.  kernels: its instantiations — [0] the one that scatters nothing into the gradient buffer (runs when
+// no Gaussian gradient is to be formed and the unit has `own_work`; else null), [1] plain atomics, [2] the wave merge — each taking
+// (RenderArgs, BwdArgs) of grt_bwd.h and, where `arg` is set, the unit's own struct behind them (RayOut, FeatArgs).  own_work: the
+// unit writes something that is no Gaussian gradient group (the rays' gradients, the feature gradient), so it runs without one.
+struct BwdUnit {
+    const void* const* kernels;
+    void* arg;
+    bool own_work;
+};
+// The backward launch: gradient buffers, lane_launch, the flush.
 int bwd_launch(grt_ctx* c, const grt_params* p, const RenderArgs& a, const float* d_grad_rgbf, const float* d_grad_alpha,
-               const grt_gaussian_grads* g, float* d_ray_grads, const void* const kernels[3], void* stream, const char* fn);
+               const grt_gaussian_grads* g, const BwdUnit& u, void* stream, const char* fn);
 }  // namespace grt

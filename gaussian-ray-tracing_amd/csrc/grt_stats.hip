@@ -2,14 +2,12 @@
 // grt_particle_stats_rays): for every particle the sum and the peak of its compositing weights T_i alpha_i and the
 // number of its composited events, over the rays of a window or of a ray buffer.
 //
-// k_particle_stats<MERGE> is ONE sweep of the backward's body (grt_bwd.h: backward_body) without colour: lane_ray gives the ray, one
-// ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round (grt_kround.h) through a single call site, every lane of the wave in
-// step.  Per slot of the k-buffers the wave scatters as scatter<MERGE> does: the lanes that hold the same particle form a group
-// (ballot / readlane); the group's count is the popcount of its ballot, its sum wave_sum, its peak wave_max (grt_wave.h), and
+// k_particle_stats<MERGE> is ONE sweep_events call (grt_bwd.h) without colour: lane_ray gives the ray, one ray per lane, an 8x8 tile
+// per wave, every lane of the wave in step.  Per slot of the k-buffers the wave scatters through wave_groups as scatter<MERGE>
+// does: of the lanes that hold the same particle the group's count is its size, its sum wave_sum, its peak wave_max (grt_wave.h), and
 // its leader issues one atomic per requested output; a lane alone with its particle issues its own.  MERGE = false
 // (GRT_OPT_BWD_PLAIN_ATOMICS = 1): every lane issues its own.  The atomics go straight into the caller's arrays: float add,
 // unsigned max on the bit pattern of a non-negative float, unsigned add.  The context owns no buffer for this.
-#include <algorithm>
 #include <string>
 
 #include "grt_bwd.h"
@@ -42,24 +40,12 @@ __device__ __forceinline__ void stats_scatter(const StatsArgs& s, bool ev, uint3
         if (ev) stats_add(s, id, ws, w, 1u);
         return;
     }
-    uint64_t todo = __builtin_amdgcn_ballot_w64(ev);
-    bool solo = false;
-    while (todo) { // wave-uniform
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t lid = (uint32_t)__builtin_amdgcn_readlane((int)id, leader);
-        const bool mine = ev && id == lid;
-        const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
-        todo &= ~m;
-        const uint32_t n = (uint32_t)__builtin_popcountll(m);
-        if (n == 1u) { // alone with its particle: its own atomics, once the groups are done
-            solo = solo || mine;
-            continue;
-        }
+    const bool solo = wave_groups(ev, id, [&](uint32_t lid, bool mine, uint32_t n, uint32_t leader) {
         float sum = 0.0f, peak = 0.0f;
         if (s.weight_sum) sum = wave_sum(mine ? ws : 0.0f);
         if (s.weight_max) peak = wave_max(mine ? w : 0.0f);
-        if (lane == (uint32_t)leader) stats_add(s, lid, sum, peak, n);
-    }
+        if (lane == leader) stats_add(s, lid, sum, peak, n);
+    });
     if (solo) stats_add(s, id, ws, w, 1u);
 }
 
@@ -82,52 +68,13 @@ __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, c
     }
     if (!__builtin_amdgcn_ballot_w64(live)) return; // wave-uniform
 
-    const rayinv ri = mk_rayinv(o, d);
-    const float epsT = 1e-9f;
-    const float t_max = a.p.t_max;
-    const float t_hi = t_max + epsT;
-    const float minT = a.p.minTransmittance;
-    KBuf<K> kb;
-    grt::Cnt cnt; // (dead: no counters, no watchdog)
-
-    // one sweep over the events trace() composites (shaders/tracer.cuh:328-373), every lane of the wave in step: the scatter is
-    // wave-cooperative, a finished lane idles
-    float T = 1.0f, lastT = a.p.t_min;
-    uint64_t last_key = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
-    bool act = live && (lastT <= t_max) && (T > minT);
-    while (__builtin_amdgcn_ballot_w64(act)) {
-        if (act) {
-            gps_round<false, false, K>(a, stk, o, d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
-            if (kb.key[0] == kKeyInvalid) act = false;
-        }
-#pragma unroll 1
-        for (int i = 0; i < K; i++) {
-            bool ev = false;
-            uint32_t id = 0;
-            float w = 0.0f;
-            uint64_t key = kKeyInvalid;
-            float hitAlpha = 0.0f;
-#pragma unroll
-            for (int j = 0; j < K; j++) {
-                if (j == i) { key = kb.key[j]; hitAlpha = kb.alpha[j]; }
-            }
-            if (act && key != kKeyInvalid && T > minT) {
-                lastT = fmaxf(key_t(key), lastT);
-                if (a.p.alpha_min < hitAlpha) {
-                    ev = true;
-                    id = key_id(key);
-                    w = T * hitAlpha; // T: the transmittance before the event
-                    T *= (1.0f - hitAlpha);
-                }
-            }
-            stats_scatter<MERGE>(s, ev, id, wr * w, w, lane);
-        }
-        if (act) {
-            if (kb.key[K - 1] == kKeyInvalid) act = false;
-            else last_key = kb.key[K - 1];
-            act = act && (lastT <= t_max) && (T > minT);
-        }
-    }
+    // one sweep over the composited events (sweep_events: the scatter is wave-cooperative, a finished lane idles)
+    float T = 1.0f;
+    sweep_events(a, stk, o, d, mk_rayinv(o, d), a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha) {
+        float w = 0.0f;
+        if (ev) w = Tb * hitAlpha; // Tb: the transmittance before the event
+        stats_scatter<MERGE>(s, ev, id, wr * w, w, lane);
+    });
 }
 
 } // namespace
@@ -135,16 +82,10 @@ __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, c
 
 using namespace grt;
 
-// what both entry points refuse before they look at their rays: the backward's refusals in the entry point's name, and a scene with meshes
+// what both entry points refuse before they look at their rays: the backward's refusals in the entry point's name, a scene with meshes in this unit's words
 static int fill(grt_ctx* c, const grt_params* p, RenderArgs* a, const char* fn)
 {
-    if (!c) return GRT_ERR_INVALID;
-    const grt_ctx* sc = scene_of(c);
-    if (p && sc->built && sc->n_faces) {
-        c->err = std::string(fn) + ": meshes are set (particle statistics are computed for Gaussian-only frames)";
-        return GRT_ERR_INVALID;
-    }
-    return bwd_fill_args(c, p, false, a, fn);
+    return bwd_fill_args(c, p, false, a, fn, "particle statistics are computed for Gaussian-only frames");
 }
 
 static int launch(grt_ctx* c, const RenderArgs& a, const float* d_ray_weight, const grt_particle_stats* out, void* stream, const char* fn)
@@ -158,21 +99,13 @@ static int launch(grt_ctx* c, const RenderArgs& a, const float* d_ray_weight, co
     if (a.n_blocks == 0 || sc->n == 0 || sc->gbvh.root_ref == kNoRoot) { c->have_timing = false; return GRT_OK; }
     CHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint32_t depth = std::max(sc->gbvh.height, 1u);
-    const size_t lds = (size_t)kBlock * sizeof(uint32_t) * depth; // one LDS stack per lane
-    if (lds > 160 * 1024) { c->err = std::string(fn) + ": BVH height " + std::to_string(depth) + " needs more than 160 KiB of LDS stack"; return GRT_ERR_LIMIT; }
     StatsArgs sa;
     sa.ray_weight = d_ray_weight;
     sa.weight_sum = out->weight_sum; sa.weight_max = out->weight_max; sa.count = out->count;
     const void* fnk = c->opt_bwd_plain ? reinterpret_cast<const void*>(k_particle_stats<false>) : reinterpret_cast<const void*>(k_particle_stats<true>);
-    CHK(c, hipFuncSetAttribute(fnk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CHK(c, hipEventRecord(c->ev0, s));
     void* args[2] = {const_cast<RenderArgs*>(&a), &sa};
-    (void)hipLaunchKernel(fnk, dim3(a.n_blocks), dim3(kBlock), args, lds, s);
-    CHK(c, hipGetLastError());
-    CHK(c, hipEventRecord(c->ev1, s));
-    c->have_timing = true;
-    return GRT_OK;
+    int rc = lane_launch(c, a, fnk, args, s, fn);
+    return rc != GRT_OK ? rc : lane_launch_done(c, s);
 }
 
 extern "C" {
