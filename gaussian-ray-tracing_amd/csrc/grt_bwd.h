@@ -1,7 +1,7 @@
 // grt_bwd.h — the device text the units that walk a ray's composited events share (grt_backward.hip, grt_backward_rays.hip,
-// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip): the kernels' arguments, a
-// lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics and
-// the feature kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
+// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip, grt_picks.hip): the kernels' arguments, a
+// lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics, the
+// feature and the pick kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
 // grouping of a wave's lanes by particle (wave_groups), the terms of one composited event, the scatter into the gradient buffer, and
 // the ONE body of k_backward<MERGE> and k_backward_rays<MERGE, GAUSS>.
 //
@@ -312,8 +312,9 @@ __device__ __forceinline__ bool load_upstream(const BwdArgs& b, size_t idx, bool
 // single call site until the segment [t_min, t_max] or the transmittance runs out, and per round the K slots of the k-buffer in
 // order — the forward's events in the forward's order.  stk: the lane's LDS stack; part: this lane takes part at all; T: the
 // transmittance, carried in and out (1, or what the ray's earlier segments left).  For every slot of every round the WHOLE wave calls
-// on_slot(ev, id, Tb, hitAlpha) once: ev — this lane composites an event in the slot, of particle id with alpha hitAlpha, at
-// transmittance Tb before it (ev false: id 0, nothing to use); T *= 1 - hitAlpha follows the call.
+// on_slot(ev, id, Tb, hitAlpha, key) once: ev — this lane composites an event in the slot, of particle id with alpha hitAlpha, at
+// transmittance Tb before it, under the k-buffer's key (key_t: the event's distance; ev false: id 0, nothing to use); T *= 1 -
+// hitAlpha follows the call.
 //
 // Wave convergence: on_slot may hold wave operations (scatter<MERGE>: DPP, v_readlane), so every lane of the wave reaches it for
 // every slot of every round.  The round loop is entered and left on a ballot over the lanes' own `act`, the slot loop has a constant
@@ -356,7 +357,7 @@ __device__ __forceinline__ void sweep_events(const RenderArgs& a, uint32_t* stk,
                     id = key_id(key);
                 }
             }
-            on_slot(ev, id, T, hitAlpha);
+            on_slot(ev, id, T, hitAlpha, key);
             if (ev) T *= (1.0f - hitAlpha);
         }
         if (act) {

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void k_render_features(const RenderArgs a, 
 
     if (__builtin_amdgcn_ballot_w64(live)) { // wave-uniform
         float T = 1.0f;
-        sweep_events(a, stk, o, d, mk_rayinv(o, d), a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha) {
+        sweep_events(a, stk, o, d, mk_rayinv(o, d), a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha, uint64_t) {
             if (ev) {
                 const float* fr = f.feat + (size_t)id * C;
                 const float w = Tb * hitAlpha; // Tb: the transmittance before the event
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_backward_features(const RenderArgs a
 #pragma unroll 1
     for (int pass = GEOM ? 0 : 1; pass < 2; pass++) {
         float T = 1.0f, P = 0.0f;
-        sweep_events(a, stk, o, d, ri, a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha) {
+        sweep_events(a, stk, o, d, ri, a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha, uint64_t) {
             bool geom = false;
             float w = 0.0f;
             float v[kVals];

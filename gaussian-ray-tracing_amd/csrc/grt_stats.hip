@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, c
 
     // one sweep over the composited events (sweep_events: the scatter is wave-cooperative, a finished lane idles)
     float T = 1.0f;
-    sweep_events(a, stk, o, d, mk_rayinv(o, d), a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha) {
+    sweep_events(a, stk, o, d, mk_rayinv(o, d), a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha, uint64_t) {
         float w = 0.0f;
         if (ev) w = Tb * hitAlpha; // Tb: the transmittance before the event
         stats_scatter<MERGE>(s, ev, id, wr * w, w, lane);

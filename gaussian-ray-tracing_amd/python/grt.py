@@ -94,6 +94,16 @@ class ParticleStats(C.Structure):
     _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("count", C.c_void_p)]
 
 
+class PickOut(C.Structure):
+    """grt_pick_out (include/grt.h): device pointers of one rule's id / t / weight arrays, each may be NULL."""
+    _fields_ = [("id", C.c_void_p), ("t", C.c_void_p), ("weight", C.c_void_p)]
+
+
+class RayPicks(C.Structure):
+    """grt_ray_picks (include/grt.h): the three rules' outputs and the transmittance the cross rule waits for."""
+    _fields_ = [("first", PickOut), ("peak", PickOut), ("cross", PickOut), ("cross_T", C.c_float)]
+
+
 class FeatureGrads(C.Structure):
     """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
@@ -111,6 +121,9 @@ REASON_NONE, REASON_FIRST_BUILD, REASON_N_CHANGED, REASON_SET_CHANGED, REASON_OP
 GRAD_SHAPES = {"pos": (3,), "scale": (3,), "quat": (4,), "opacity": (), "sh": (16, 3)}
 STATS_OUTPUTS = ("weight_sum", "weight_max", "count")
 MAX_FEATURE_CHANNELS = 16  # GRT_MAX_FEATURE_CHANNELS
+PICK_NONE = 0xFFFFFFFF     # GRT_PICK_NONE
+PICK_RULES = ("first", "peak", "cross")
+PICK_FIELDS = ("id", "t", "weight")
 FEATURE_GROUPS = ("pos", "scale", "quat", "opacity", "feat")
 
 
@@ -146,7 +159,7 @@ EXPORTS = [
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_debug_order_units",
     "grt_debug_order_scratch_bytes", "grt_debug_estimate_costs", "grt_debug_copy_schedule", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
-    "grt_particle_stats_frame", "grt_particle_stats_rays",
+    "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
@@ -207,6 +220,8 @@ def lib():
         L.grt_backward_rays_mesh.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_particle_stats_frame.argtypes = [vp, C.POINTER(Params), vp, C.POINTER(ParticleStats), u32, u32, u32, u32, vp]
         L.grt_particle_stats_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(ParticleStats), vp]
+        L.grt_ray_picks_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayPicks), u32, u32, u32, u32, vp]
+        L.grt_ray_picks_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayPicks), vp]
         L.grt_render_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, vp]
         L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
         L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
@@ -737,6 +752,46 @@ class Tracer:
             x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
             self._check(lib().grt_particle_stats_frame(self._h, C.byref(params), wp, C.byref(ptrs), x0, y0, x1, y1, self._stream()))
         return into
+
+    def ray_picks(self, params, rays=None, window=None, cross_T=0.5, picks=PICK_RULES, fields=PICK_FIELDS):
+        """grt_ray_picks_frame / grt_ray_picks_rays (rays [n][6] given): per ray the first composited event, the event of largest
+        weight T_i * alpha_i ('peak') and the first event behind which the transmittance is <= cross_T ('cross'; 0.5: the median
+        depth) -> {pick: {field: tensor}} of shape [h][w] or [n] on the tracer's GPU; include/grt.h.  'id' is the particle's original
+        id (uint32; PICK_NONE where the ray has no such event — .to(torch.int64) to index with it), 't' the event's distance and
+        'weight' its T_i * alpha_i (float32; 0 where none).  The tensors are allocated pre-filled with PICK_NONE, 0, 0, so pixels
+        outside a window and rays that are not traced read as "none".  Bitwise reproducible; nothing here is differentiable."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        picks, fields = tuple(picks), tuple(fields)
+        if not picks or any(k not in PICK_RULES for k in picks):
+            raise GrtError(f"ray_picks: picks must be a non-empty subset of {PICK_RULES}, not {picks}")
+        if not fields or any(k not in PICK_FIELDS for k in fields):
+            raise GrtError(f"ray_picks: fields must be a non-empty subset of {PICK_FIELDS}, not {fields}")
+        if "cross" in picks and not 0.0 < float(cross_T) < 1.0:
+            raise GrtError(f"ray_picks: cross_T must lie in (0, 1), not {cross_T}")
+        if rays is not None:
+            if window is not None:
+                raise GrtError("ray_picks: rays and window exclude each other")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"ray_picks: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        # (PICK_NONE is int32 -1: filled as such, the kernels of the wider unsigned types are not everywhere)
+        out = {k: {f: (t.full(shape, -1, dtype=t.int32, device=dev).view(t.uint32) if f == "id" else t.zeros(shape, dtype=t.float32, device=dev))
+                   for f in PICK_FIELDS if f in fields} for k in PICK_RULES if k in picks}
+        if not n or not shape[0] or not shape[-1]:  # (an empty scene or no ray: every element is "none" already)
+            return out
+        ptrs = RayPicks(*(PickOut(*(out[k][f].data_ptr() if k in out and f in out[k] else None for f in PICK_FIELDS)) for k in PICK_RULES),
+                        float(cross_T))
+        if rays is not None:
+            self._check(lib().grt_ray_picks_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], C.byref(ptrs), self._stream()))
+        else:
+            x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
+            self._check(lib().grt_ray_picks_frame(self._h, C.byref(params), C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return out
 
     def _feature_inputs(self, what, params, feat, rays, window):
         """feat [n_particles][C] and rays [n][6] (or None) as contiguous float32 tensors on the tracer's GPU, the shape of the rays'

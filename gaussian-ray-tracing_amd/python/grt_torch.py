@@ -22,6 +22,11 @@ grt_torch.render included), and raises GrtError otherwise.  This is the only mod
 
 composites the caller's own per-particle channels with the weights of the scene the tracer holds, differentiable
 with respect to feat and to the four geometry tensors of the last upload; it uploads nothing, so it shares a backward with render().
+
+    picks = grt_torch.ray_picks(tracer, params, cross_T=0.5)      # {"first", "peak", "cross": {"id", "t", "weight": [h][w]}}
+
+says which particle every ray of that scene sees first, strongest and where its transmittance falls to cross_T (the median depth at
+0.5), by original id: picking, lasso selection, id maps.  Discrete, so nothing of it is differentiable.
 """
 import numpy as np
 import torch
@@ -151,6 +156,20 @@ def particle_stats(tracer, params, rays=None, ray_weight=None, into=None):
     differentiable: the tensors carry no graph."""
     with torch.no_grad():
         return tracer.particle_stats(params, rays=rays, ray_weight=ray_weight, into=into)
+
+
+def ray_picks(tracer, params, rays=None, window=None, cross_T=0.5, picks=grt.PICK_RULES, fields=grt.PICK_FIELDS):
+    """Per-ray picks of the frame (or of its `window`, or of `rays` [n][6]) under torch.no_grad(): {pick: {field: tensor}} for the
+    picks 'first', 'peak' and 'cross' and the fields 'id' (uint32, grt.PICK_NONE where the ray has no such event), 't' and 'weight'
+    (Tracer.ray_picks; include/grt.h: grt_ray_picks_frame / grt_ray_picks_rays) — which particle every ray sees first, strongest and
+    where its transmittance falls to cross_T (0.5: the median depth), for picking, lasso selection, id maps and surface depth.
+    Like particle_stats it reads the scene the tracer HOLDS and uploads nothing: call it right after grt_torch.render(tracer, ...).
+    The picks are discrete: nothing here is differentiable, the tensors carry no graph, and `rays` that requires grad is refused
+    (ValueError), as render_features refuses it."""
+    if rays is not None and rays.requires_grad:
+        raise ValueError("grt_torch.ray_picks: picks are discrete and carry no gradient with respect to rays; detach rays")
+    with torch.no_grad():
+        return tracer.ray_picks(params, rays=rays, window=window, cross_T=cross_T, picks=picks, fields=fields)
 
 
 class _RenderFeatures(torch.autograd.Function):

@@ -652,6 +652,47 @@ GRT_API int grt_backward_features_frame(grt_ctx* ctx, const grt_params* p, const
                                         const grt_feature_grads* grads, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_backward_features_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_feat,
                                        uint32_t channels, const float* d_grad_out, const grt_feature_grads* grads, void* stream);
+/* ---- per-ray picks: which particle a ray sees first, strongest and at its median, and where (Gaussian-only frames) ----
+ * What picking and lasso selection in a viewer, per-pixel id and label maps, and a surface depth (TSDF fusion, mesh extraction, depth
+ * regularisers) read: grt_aux_out::depth is the expected distance sum w_i t_i and smears across silhouettes; the particle statistics
+ * are per particle, not per pixel.  A COMPOSITED EVENT is exactly the backward pass's, the statistics' and the features' (above): the
+ * k-buffer's events i in key order (t, id, entry < exit), BOTH the entry and the exit event of a proxy, repeats of a split particle's
+ * pieces dropped, an event counted when alpha_min < alpha_i, the walk going on while T > minTransmittance and the last distance
+ * <= t_max.  Its weight is w_i = T_i alpha_i, T_i the transmittance BEFORE the event: ONE float32 product of the forward's own two
+ * factors, as for the statistics.  Per ray, three rules select one event each:
+ *     first    the first composited event
+ *     peak     the event of largest w_i; a later event replaces the pick only when its weight is STRICTLY greater (the earliest wins a tie)
+ *     cross    the first event i with T_i (1 - alpha_i) <= cross_T: the float32 transmittance BEHIND the event, as the compositing loop
+ *              forms it.  cross_T = 0.5 gives the median depth.
+ * and for each rule the call writes
+ *     id       the particle's ORIGINAL id (it indexes the arrays of grt_gaussians), GRT_PICK_NONE where there is no such event
+ *     t        the event's key distance — the t_i of grt_aux_out::depth, in units of |d| for caller-supplied rays — else 0.0f
+ *     weight   w_i, else 0.0f
+ * Every element of the window ([h][w], laid out like the frame) or of the buffer ([n]) is WRITTEN exactly once per requested array:
+ * GRT_PICK_NONE, 0.0f, 0.0f for a ray with no such event and for a ray that is not traced (fisheye r > 1, |d| <= 0.1, a NaN direction,
+ * max_bounces = 0, an empty tree or an empty scene); pixels outside the window are untouched.  Each of the nine arrays may be NULL (it
+ * is not written).  No atomic is in the path: the call is BITWISE reproducible, and windows tile a frame bit for bit.
+ * The call uses no buffer of the context (grt_memory_info::slot_bytes is unchanged by it); a frame rendered after it is bit-identical
+ * to one rendered before it; a view computes its scene's result.  Asynchronous on `stream` like grt_render; grt_last_kernel_ms
+ * reports the call's device time.  With n = 0 rays or an empty window the call returns GRT_OK and writes nothing.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): everything
+ * grt_particle_stats_* refuses (GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a window outside the frame, sh_degree_max > 3,
+ * t_min <= 0), meshes set (ray picks are computed for Gaussian-only frames), all nine pointers NULL, cross_T outside (0, 1) (NaN
+ * included) while any array of `cross` is requested.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB, as
+ * in the statistics.  Not computed: more than one pick per rule, gradients of any kind, mesh frames. */
+#define GRT_PICK_NONE 0xFFFFFFFFu
+typedef struct {
+    uint32_t* id;
+    float* t;
+    float* weight;
+} grt_pick_out; /* each may be NULL */
+typedef struct {
+    grt_pick_out first, peak, cross;
+    float cross_T;
+} grt_ray_picks;
+GRT_API int grt_ray_picks_frame(grt_ctx* ctx, const grt_params* p, const grt_ray_picks* out, uint32_t x0, uint32_t y0, uint32_t x1,
+                                uint32_t y1, void* stream);
+GRT_API int grt_ray_picks_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_ray_picks* out, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
