@@ -1,9 +1,10 @@
 // grt_bwd.h — the device text the units that walk a ray's composited events share (grt_backward.hip, grt_backward_rays.hip,
-// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip, grt_picks.hip): the kernels' arguments, a
+// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip, grt_picks.hip, grt_events.hip; DESIGN.md 5.8, 5.10, 5.11, 5.12, 5.17, 5.18, 5.19,
+// 5.20): the kernels' arguments, a
 // lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics, the
-// feature and the pick kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
-// grouping of a wave's lanes by particle (wave_groups), the terms of one composited event, the scatter into the gradient buffer, and
-// the ONE body of k_backward<MERGE> and k_backward_rays<MERGE, GAUSS>.
+// feature, the pick and the event-list kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
+// grouping of a wave's lanes by particle (wave_groups), the terms of one composited event (event_terms, and below one alpha: alpha_terms),
+// the scatter into the gradient buffer, and the ONE body of k_backward<MERGE> and k_backward_rays<MERGE, GAUSS>.
 //
 // One ray per lane, an 8x8 tile per wave, k = 7 rounds of gps_round (grt_kround.h: the round trace_gaussians of grt_render.hip
 // runs, without its watchdog and counters), twice per ray:
@@ -165,6 +166,65 @@ __device__ __forceinline__ void scatter(float* __restrict__ acc, bool ev, uint32
     if (solo) scatter_own(acc, id, v, geom, colour);
 }
 
+// The chain below one event's alpha = min(0.99, opacity r): v[0..10] = dLda * d alpha / d (pos 3, scale 3, quat 4, opacity) of particle
+// id for the ray (o, d), where the 0.99 clamp does not bind (the caller's test).  dLda: dloss/dalpha of the event — event_terms forms it
+// from the radiance and the density behind the event, k_backward_events (grt_events.hip) is handed it.  RAYS: m = A^T g_p (v[0..2])
+// goes to the origin's and d_val m to the direction's gradient in ra.
+template <bool RAYS>
+__device__ __forceinline__ void alpha_terms(const BwdArgs& b, uint32_t id, f3 o, f3 d, float dLda, float v[kVals], RayAcc& ra)
+{
+    const f3 mu = mk3(b.pos[id * 3], b.pos[id * 3 + 1], b.pos[id * 3 + 2]);
+    const float opac = b.opacity[id];
+    const float is[3] = {1.0f / b.scale[id * 3], 1.0f / b.scale[id * 3 + 1], 1.0f / b.scale[id * 3 + 2]};
+    const float qw = b.quat[id * 4], qx = b.quat[id * 4 + 1], qy = b.quat[id * 4 + 2], qz = b.quat[id * 4 + 3];
+    float Rg[9];
+    mat3_cast(qw, qx, qy, qz, Rg);
+    m33 A; // as k_gather_records forms it (grt_scene.hip)
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) A.a[r * 3 + c] = is[r] * Rg[r * 3 + c];
+    }
+    // computeResponse (grt_device.h: response_from), keeping v = mu - (o + d_val d) and p_g = A v
+    const f3 o_g = matvec(A, sub3(o, mu));
+    const f3 d_g = matvec(A, d);
+    const float d_val = -dot3(o_g, d_g) / fmaxf(1e-6f, dot3(d_g, d_g));
+    const f3 vv = sub3(mu, add3(o, mul3s(d, d_val)));
+    const f3 p_g = matvec(A, vv);
+    const float r = exp_nonpos(-0.5f * dot3(p_g, p_g));
+    v[10] = dLda * r;                 // d alpha / d opacity = r
+    const float gr = -(dLda * opac) * r; // d r / d p_g = -r p_g
+    const f3 gp = mk3(gr * p_g.x, gr * p_g.y, gr * p_g.z);
+    // d/d mu = A^T g_p
+    v[0] = A.a[0] * gp.x + A.a[3] * gp.y + A.a[6] * gp.z;
+    v[1] = A.a[1] * gp.x + A.a[4] * gp.y + A.a[7] * gp.z;
+    v[2] = A.a[2] * gp.x + A.a[5] * gp.y + A.a[8] * gp.z;
+    if (RAYS) { // d p_g / d o = -A, d p_g / d d = -d_val A (at fixed d_val)
+        ra.go = add3(ra.go, mk3(v[0], v[1], v[2]));
+        ra.gd = add3(ra.gd, mk3(d_val * v[0], d_val * v[1], d_val * v[2]));
+    }
+    // d/d s_k = -g_p,k (R^T v)_k / s_k^2 = -g_p,k p_g,k / s_k
+    v[3] = -(gp.x * p_g.x) * is[0];
+    v[4] = -(gp.y * p_g.y) * is[1];
+    v[5] = -(gp.z * p_g.z) * is[2];
+    // d/d R_jk = v_j g_p,k / s_k, then through glm::mat3_cast
+    const float h[3] = {gp.x * is[0], gp.y * is[1], gp.z * is[2]};
+    const float vj[3] = {vv.x, vv.y, vv.z};
+    float G[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) G[j][k] = vj[j] * h[k];
+    }
+    v[6] = 2.0f * (((qz * (G[1][0] - G[0][1])) + (qy * (G[0][2] - G[2][0]))) + (qx * (G[2][1] - G[1][2])));
+    v[7] = 2.0f * ((((qy * (G[0][1] + G[1][0])) + (qz * (G[0][2] + G[2][0]))) + (qw * (G[2][1] - G[1][2]))) -
+                   2.0f * qx * (G[1][1] + G[2][2]));
+    v[8] = 2.0f * ((((qx * (G[0][1] + G[1][0])) + (qz * (G[1][2] + G[2][1]))) + (qw * (G[0][2] - G[2][0]))) -
+                   2.0f * qy * (G[0][0] + G[2][2]));
+    v[9] = 2.0f * ((((qx * (G[0][2] + G[2][0])) + (qy * (G[1][2] + G[2][1]))) + (qw * (G[1][0] - G[0][1]))) -
+                   2.0f * qz * (G[0][0] + G[1][1]));
+}
+
 // The terms of one composited event (sweep 1): v[0..13] = what it adds to pos 3, scale 3, quat 4, opacity, sh_0 3 of particle id (the
 // higher SH coefficients go to their buffer from here: one lane, one direction — nothing to merge across the wave).  T: the
 // transmittance before the event; S: what lies behind it (rad - C_<=i).  Returns whether the geometry / opacity terms were formed.
@@ -203,56 +263,7 @@ __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& 
     }
     if (b.want_geom && hitAlpha < 0.99f) { // (where the 0.99 clamp binds nothing goes into opacity or geometry)
         geom = true;
-        const f3 mu = mk3(b.pos[id * 3], b.pos[id * 3 + 1], b.pos[id * 3 + 2]);
-        const float opac = b.opacity[id];
-        const float is[3] = {1.0f / b.scale[id * 3], 1.0f / b.scale[id * 3 + 1], 1.0f / b.scale[id * 3 + 2]};
-        const float qw = b.quat[id * 4], qx = b.quat[id * 4 + 1], qy = b.quat[id * 4 + 2], qz = b.quat[id * 4 + 3];
-        float Rg[9];
-        mat3_cast(qw, qx, qy, qz, Rg);
-        m33 A; // as k_gather_records forms it (grt_scene.hip)
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.a[r * 3 + c] = is[r] * Rg[r * 3 + c];
-        }
-        // computeResponse (grt_device.h: response_from), keeping v = mu - (o + d_val d) and p_g = A v
-        const f3 o_g = matvec(A, sub3(o, mu));
-        const f3 d_g = matvec(A, d);
-        const float d_val = -dot3(o_g, d_g) / fmaxf(1e-6f, dot3(d_g, d_g));
-        const f3 vv = sub3(mu, add3(o, mul3s(d, d_val)));
-        const f3 p_g = matvec(A, vv);
-        const float r = exp_nonpos(-0.5f * dot3(p_g, p_g));
-        v[10] = dLda * r;                 // d alpha / d opacity = r
-        const float gr = -(dLda * opac) * r; // d r / d p_g = -r p_g
-        const f3 gp = mk3(gr * p_g.x, gr * p_g.y, gr * p_g.z);
-        // d/d mu = A^T g_p
-        v[0] = A.a[0] * gp.x + A.a[3] * gp.y + A.a[6] * gp.z;
-        v[1] = A.a[1] * gp.x + A.a[4] * gp.y + A.a[7] * gp.z;
-        v[2] = A.a[2] * gp.x + A.a[5] * gp.y + A.a[8] * gp.z;
-        if (RAYS) { // d p_g / d o = -A, d p_g / d d = -d_val A (at fixed d_val)
-            ra.go = add3(ra.go, mk3(v[0], v[1], v[2]));
-            ra.gd = add3(ra.gd, mk3(d_val * v[0], d_val * v[1], d_val * v[2]));
-        }
-        // d/d s_k = -g_p,k (R^T v)_k / s_k^2 = -g_p,k p_g,k / s_k
-        v[3] = -(gp.x * p_g.x) * is[0];
-        v[4] = -(gp.y * p_g.y) * is[1];
-        v[5] = -(gp.z * p_g.z) * is[2];
-        // d/d R_jk = v_j g_p,k / s_k, then through glm::mat3_cast
-        const float h[3] = {gp.x * is[0], gp.y * is[1], gp.z * is[2]};
-        const float vj[3] = {vv.x, vv.y, vv.z};
-        float G[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) G[j][k] = vj[j] * h[k];
-        }
-        v[6] = 2.0f * (((qz * (G[1][0] - G[0][1])) + (qy * (G[0][2] - G[2][0]))) + (qx * (G[2][1] - G[1][2])));
-        v[7] = 2.0f * ((((qy * (G[0][1] + G[1][0])) + (qz * (G[0][2] + G[2][0]))) + (qw * (G[2][1] - G[1][2]))) -
-                       2.0f * qx * (G[1][1] + G[2][2]));
-        v[8] = 2.0f * ((((qx * (G[0][1] + G[1][0])) + (qz * (G[1][2] + G[2][1]))) + (qw * (G[0][2] - G[2][0]))) -
-                       2.0f * qy * (G[0][0] + G[2][2]));
-        v[9] = 2.0f * ((((qx * (G[0][2] + G[2][0])) + (qy * (G[1][2] + G[2][1]))) + (qw * (G[1][0] - G[0][1]))) -
-                       2.0f * qz * (G[0][0] + G[1][1]));
+        alpha_terms<RAYS>(b, id, o, d, dLda, v, ra);
     }
     return geom;
 }

@@ -104,6 +104,13 @@ class RayPicks(C.Structure):
     _fields_ = [("first", PickOut), ("peak", PickOut), ("cross", PickOut), ("cross_T", C.c_float)]
 
 
+class RayEvents(C.Structure):
+    """grt_ray_events (include/grt.h): device pointers of the slot-major id / t / alpha arrays [K][N] and of count / T_in [N], each may
+    be NULL; the first listed event and K = max_events."""
+    _fields_ = [("id", C.c_void_p), ("t", C.c_void_p), ("alpha", C.c_void_p), ("count", C.c_void_p), ("T_in", C.c_void_p),
+                ("first", C.c_uint32), ("max_events", C.c_uint32)]
+
+
 class FeatureGrads(C.Structure):
     """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
@@ -125,6 +132,8 @@ PICK_NONE = 0xFFFFFFFF     # GRT_PICK_NONE
 PICK_RULES = ("first", "peak", "cross")
 PICK_FIELDS = ("id", "t", "weight")
 FEATURE_GROUPS = ("pos", "scale", "quat", "opacity", "feat")
+EVENT_FIELDS = ("id", "t", "alpha", "count", "T_in")
+EVENT_GROUPS = ("pos", "scale", "quat", "opacity")
 
 
 class Mesh(C.Structure):
@@ -160,6 +169,7 @@ EXPORTS = [
     "grt_debug_order_scratch_bytes", "grt_debug_estimate_costs", "grt_debug_copy_schedule", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
     "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
+    "grt_ray_events_frame", "grt_ray_events_rays", "grt_backward_events_frame", "grt_backward_events_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
@@ -222,6 +232,10 @@ def lib():
         L.grt_particle_stats_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(ParticleStats), vp]
         L.grt_ray_picks_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayPicks), u32, u32, u32, u32, vp]
         L.grt_ray_picks_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayPicks), vp]
+        L.grt_ray_events_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayEvents), u32, u32, u32, u32, vp]
+        L.grt_ray_events_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayEvents), vp]
+        L.grt_backward_events_frame.argtypes = [vp, C.POINTER(Params), vp, u32, u32, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
+        L.grt_backward_events_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, u32, C.POINTER(GaussianGrads), vp]
         L.grt_render_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, vp]
         L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
         L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
@@ -792,6 +806,84 @@ class Tracer:
             x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
             self._check(lib().grt_ray_picks_frame(self._h, C.byref(params), C.byref(ptrs), x0, y0, x1, y1, self._stream()))
         return out
+
+    def _event_inputs(self, what, params, rays, window, max_events, first):
+        """rays [n][6] (or None) as a contiguous float32 tensor on the tracer's GPU, the shape of one slot plane, the window, K and first."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        K, first = int(max_events), int(first)
+        if K < 1 or first < 0 or first + K > 0xFFFFFFFF:
+            raise GrtError(f"{what}: max_events must be >= 1 and first >= 0 with first + max_events below 2^32, not {max_events} and {first}")
+        if rays is not None:
+            if window is not None:
+                raise GrtError(f"{what}: rays and window exclude each other")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"{what}: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        return rays, shape, (window if window else (0, 0, params.width, params.height)), dev, K, first
+
+    def ray_events(self, params, rays=None, window=None, max_events=32, first=0, fields=EVENT_FIELDS):
+        """grt_ray_events_frame / grt_ray_events_rays (rays [n][6] given): every ray's own list of composited events, the events
+        first .. first + max_events - 1 in compositing order -> dict of torch tensors on the tracer's GPU; include/grt.h.  Slot-major:
+        'id' (uint32, the particle's original id, PICK_NONE in an unused slot), 't' (float32, the event's key distance) and 'alpha'
+        (float32, the alpha the forward composites) have shape [K][h][w] or [K][n]; 'count' (uint32, ALL events of the ray, not capped
+        by K) and 'T_in' (float32, the transmittance in front of event `first`) [h][w] or [n].  T = T_in * cumprod(1 - alpha, 0) are the
+        transmittances behind the listed events.  The tensors are allocated pre-filled with PICK_NONE, 0, 0, 0, 1, so pixels outside a
+        window and rays that are not traced read as "no event".  Bitwise reproducible; backward_events takes dloss/dalpha back."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, K, first = self._event_inputs("ray_events", params, rays, window, max_events, first)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        fields = tuple(fields)
+        if not fields or any(k not in EVENT_FIELDS for k in fields):
+            raise GrtError(f"ray_events: fields must be a non-empty subset of {EVENT_FIELDS}, not {fields}")
+        # (PICK_NONE is int32 -1: filled as such, the kernels of the wider unsigned types are not everywhere)
+        make = {"id": lambda: t.full((K,) + shape, -1, dtype=t.int32, device=dev).view(t.uint32),
+                "t": lambda: t.zeros((K,) + shape, dtype=t.float32, device=dev),
+                "alpha": lambda: t.zeros((K,) + shape, dtype=t.float32, device=dev),
+                "count": lambda: t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32),
+                "T_in": lambda: t.ones(shape, dtype=t.float32, device=dev)}
+        out = {k: make[k]() for k in EVENT_FIELDS if k in fields}
+        if not n or not shape[0] or not shape[-1]:  # (an empty scene or no ray: every element is "no event" already)
+            return out
+        ptrs = RayEvents(*(out[k].data_ptr() if k in out else None for k in EVENT_FIELDS), first, K)
+        if rays is not None:
+            self._check(lib().grt_ray_events_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], C.byref(ptrs), self._stream()))
+        else:
+            self._check(lib().grt_ray_events_frame(self._h, C.byref(params), C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return out
+
+    def backward_events(self, params, grad_alpha, rays=None, window=None, first=0, into=None, groups=None):
+        """grt_backward_events_frame / grt_backward_events_rays: grad_alpha [K][h][w] or [K][n] holds dloss/dalpha of the events
+        ray_events listed (same params, rays / window and first; K is its first dimension) -> dict of torch tensors pos, scale, quat,
+        opacity: the gradients with respect to the uploaded Gaussians, allocated zeroed for `groups` (default: all four) or ACCUMULATED
+        into the tensors of `into` (its keys are the groups computed).  Values in slots behind a ray's last event are ignored, a ray
+        whose column is all zero is not traced, an event where the 0.99 clamp binds adds nothing.  One traversal.  'sh' is refused:
+        colour does not depend on the listed quantities.  Not bitwise reproducible (float atomics); include/grt.h."""
+        t = self._torch
+        if not t.is_tensor(grad_alpha) or grad_alpha.dim() < 2:
+            raise GrtError("backward_events: grad_alpha must be a tensor of shape [K][h][w] or [K][n]")
+        rays, shape, (x0, y0, x1, y1), dev, K, first = self._event_inputs("backward_events", params, rays, window, grad_alpha.shape[0], first)
+        if tuple(grad_alpha.shape) != (K,) + shape:
+            raise GrtError(f"backward_events: grad_alpha must have shape [K]{list(shape)}, not {tuple(grad_alpha.shape)}")
+        grad_alpha = grad_alpha.detach().to(dev, t.float32).contiguous()
+        if "sh" in (into if into is not None else (groups if groups is not None else ())):
+            raise GrtError("backward_events: 'sh' is not a group of this call (colour does not depend on the listed events' alpha)")
+        if (into is not None and not into) or (into is None and groups is not None and not len(groups)):
+            raise GrtError("backward_events: no gradient group asked for")
+        into, ptrs = self._grad_buffers(into, groups if groups is not None else EVENT_GROUPS, dev)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if not n or not grad_alpha.numel():
+            return into
+        if rays is not None:
+            self._check(lib().grt_backward_events_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], grad_alpha.data_ptr(), first, K,
+                                                       C.byref(ptrs), self._stream()))
+        else:
+            self._check(lib().grt_backward_events_frame(self._h, C.byref(params), grad_alpha.data_ptr(), first, K, C.byref(ptrs),
+                                                        x0, y0, x1, y1, self._stream()))
+        return into
 
     def _feature_inputs(self, what, params, feat, rays, window):
         """feat [n_particles][C] and rays [n][6] (or None) as contiguous float32 tensors on the tracer's GPU, the shape of the rays'

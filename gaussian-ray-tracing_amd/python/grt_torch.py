@@ -27,6 +27,11 @@ with respect to feat and to the four geometry tensors of the last upload; it upl
 
 says which particle every ray of that scene sees first, strongest and where its transmittance falls to cross_T (the median depth at
 0.5), by original id: picking, lasso selection, id maps.  Discrete, so nothing of it is differentiable.
+
+    ev = grt_torch.ray_events(tracer, params, geometry=(pos, scale, quat, opacity), max_events=32)   # id, t, alpha [K][h][w]; count, T_in
+
+hands out every ray's own list of composited events; `alpha` carries the graph, so any per-ray loss written in torch
+on the events' alpha and distances is differentiable with respect to the four geometry tensors.
 """
 import numpy as np
 import torch
@@ -170,6 +175,69 @@ def ray_picks(tracer, params, rays=None, window=None, cross_T=0.5, picks=grt.PIC
         raise ValueError("grt_torch.ray_picks: picks are discrete and carry no gradient with respect to rays; detach rays")
     with torch.no_grad():
         return tracer.ray_picks(params, rays=rays, window=window, cross_T=cross_T, picks=picks, fields=fields)
+
+
+class _RayEvents(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, scale, quat, opacity, rays, window, tracer, params, max_events, first):
+        # pos .. opacity: the tensors of the tracer's last upload: only the carriers of the geometry gradients
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.params, ctx.window, ctx.first = tracer, params, window, first
+        ctx.rays = rays.detach() if rays is not None else None
+        ctx.like = tuple((t.device, t.dtype) for t in (pos, scale, quat, opacity))
+        out = tracer.ray_events(params, rays=ctx.rays, window=window, max_events=max_events, first=first)
+        ctx.mark_non_differentiable(out["id"], out["t"], out["count"], out["T_in"])
+        return out["id"], out["t"], out["alpha"], out["count"], out["T_in"]
+
+    @staticmethod
+    def backward(ctx, g_id, g_t, g_alpha, g_count, g_T_in):
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("pos", "scale", "quat", "opacity")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:4]) if want]
+        if not groups or g_alpha is None:
+            return (None,) * 10
+        g = tr.backward_events(ctx.params, g_alpha, rays=ctx.rays, window=ctx.window, first=ctx.first, groups=groups)
+        return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 6
+
+
+def ray_events(tracer, params, geometry=None, rays=None, window=None, max_events=32, first=0):
+    """Every ray's own list of composited events (Tracer.ray_events; include/grt.h: grt_ray_events_frame / _rays): a dict of 'id', 't',
+    'alpha' [K][h][w] (or [K][n] for `rays` [n][6]; K = max_events, the events first .. first + K - 1 in compositing order, slot-major)
+    and 'count', 'T_in' [h][w] (or [n]) on the tracer's GPU.  With T = T_in * cumprod(1 - alpha, 0) the transmittances behind the
+    events and w = alpha * T / (1 - alpha) their compositing weights, formed by the caller in torch, any per-ray loss — a distortion
+    regulariser, quantile depths, a transmittance profile, a loss on sum w t — needs no kernel of its own.
+    Without `geometry` it is the plain call under torch.no_grad().  With geometry=(pos, scale, quat, opacity) 'alpha' carries the
+    graph: a loss on it is differentiable with respect to those four (grt_backward_events_*: one traversal).  'id', 't', 'count' and
+    'T_in' carry NO gradient: t is the proxy-hit distance of the k-buffer's key, a piecewise function of the proxy's faces, and is
+    returned as data; T_in is a value, so a differentiable loss over more than K events of a ray takes a larger K, not pages.
+    It lists the scene the tracer HOLDS and uploads nothing, like render_features: grt_torch.render(tracer, ...) followed by
+    grt_torch.ray_events(tracer, ...) can share one loss.backward().  The `geometry` tensors only carry the gradient — they must be
+    the tensors of the tracer's last upload, their shapes are checked against the tracer's particle count and their values are not
+    read.  The backward raises GrtError when the tracer has received another upload since the forward.  Gradients with respect to
+    rays are not computed (`rays` that requires grad: ValueError), and neither are mesh frames (a tracer with meshes: ValueError)."""
+    if tracer.has_meshes:
+        raise ValueError("grt_torch.ray_events: meshes are set on this tracer; ray events are listed for Gaussian-only frames")
+    if rays is not None and rays.requires_grad:
+        raise ValueError("grt_torch.ray_events: gradients with respect to rays are not computed through the event list; detach rays")
+    if geometry is None:
+        with torch.no_grad():
+            return tracer.ray_events(params, rays=rays, window=window, max_events=max_events, first=first)
+    geo = tuple(geometry)
+    scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene)
+    n = scene.n_particles
+    want = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,)}
+    if len(geo) != 4 or any(not torch.is_tensor(t) for t in geo):
+        raise ValueError("grt_torch.ray_events: geometry must be four tensors (pos, scale, quat, opacity)")
+    for (name, shape), t in zip(want.items(), geo):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"grt_torch.ray_events: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
+                             f"not {tuple(t.shape)}")
+    out = _RayEvents.apply(*geo, rays, window, tracer, params, max_events, first)
+    return dict(zip(grt.EVENT_FIELDS, out))
 
 
 class _RenderFeatures(torch.autograd.Function):

@@ -693,6 +693,63 @@ typedef struct {
 GRT_API int grt_ray_picks_frame(grt_ctx* ctx, const grt_params* p, const grt_ray_picks* out, uint32_t x0, uint32_t y0, uint32_t x1,
                                 uint32_t y1, void* stream);
 GRT_API int grt_ray_picks_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_ray_picks* out, void* stream);
+/* ---- per-ray event lists with gradients: the composited events themselves, for any per-ray loss (Gaussian-only frames) ----
+ * Everything the renderer reports per pixel, per particle and per pick is computed from one thing: the ray's list of composited events
+ * (id_i, t_i, alpha_i) in compositing order.  These calls hand that list out, and take dloss/dalpha_i back: with T_i = prod_{j<i}
+ * (1 - alpha_j) and w_i = T_i alpha_i formed by the CALLER from the returned alpha, any loss on a ray's events — a depth-distortion
+ * regulariser sum_ij w_i w_j |t_i - t_j|, quantile depths, a transmittance profile, a loss on sum w_i t_i, an entropy term — is
+ * differentiable with respect to pos, scale, quat and opacity without a kernel of its own.  A COMPOSITED EVENT is exactly the picks',
+ * the features', the statistics' and the backward pass's (above): key order (t, id, entry < exit), BOTH events of a proxy, repeats of a
+ * split particle's pieces dropped, alpha_min < alpha_i, the walk going on while T > minTransmittance and the last distance <= t_max.
+ * FORWARD.  The events `first` .. `first + K - 1` of every ray (K = max_events; first = 0: the first K) go to slot s = i - first:
+ *     id     [K][N]  the particle's ORIGINAL id, GRT_PICK_NONE in an unused slot
+ *     t      [K][N]  the event's key distance — the t_i of grt_aux_out::depth and of the picks, in units of |d| for caller-supplied
+ *                    rays —, 0.0f in an unused slot.  t_i is the proxy-hit distance, a piecewise function of the proxy's faces: it is
+ *                    DATA and carries no gradient.
+ *     alpha  [K][N]  the alpha the forward composites (after the 0.99 clamp), 0.0f in an unused slot
+ *     count  [N]     ALL composited events of the ray, not capped by K (grt_aux_out::count)
+ *     T_in   [N]     the float32 transmittance in front of event `first` as the compositing loop forms it (T *= 1 - alpha, one
+ *                    multiplication per event): 1 for first = 0, the ray's final T when count <= first, 1 for a ray that is not traced
+ * N = width * height for a frame (element py * width + px, as in every per-pixel array), n for a ray buffer.  The layout is SLOT-MAJOR:
+ * element [s][r] is at s * N + r, so a slot plane is contiguous and cumprod(1 - alpha) along the first axis gives the transmittances.
+ * Every element [s][r], s < K, of the window or of the buffer is WRITTEN exactly once per requested array — GRT_PICK_NONE, 0.0f, 0.0f
+ * behind the ray's last listed event and for a ray that is not traced (fisheye r > 1, |d| <= 0.1, a NaN direction, max_bounces = 0, an
+ * empty tree or an empty scene) — and so are count and T_in; pixels outside the window are untouched.  Each of the five arrays may be
+ * NULL (it is not written).  No atomic, no wave operation and no buffer of the context (grt_memory_info::slot_bytes is unchanged): the
+ * call is BITWISE reproducible, windows tile a frame bit for bit, and pages (first = 0, K, 2K, ...) concatenate to the one long call.
+ * BACKWARD.  d_grad_alpha [K][N], laid out like alpha for the same first and max_events: g[s][r] = dloss/dalpha of the event in slot s
+ * of ray r, every discrete decision held fixed as in grt_backward.  The call ADDS
+ *     sum over the listed events of  g[s][r] * d alpha_i / d (pos, scale, quat, opacity)
+ * into the caller's arrays ([n][3] [n][3] [n][4] [n] by original id; the caller zeroes them) — grt_backward's own chain below alpha_i,
+ * the quaternion AS UPLOADED, nothing where the 0.99 clamp binds (alpha_i = 0.99 does not move).  Values of g in slots behind a ray's
+ * last listed event are NOT read as gradients of anything; a ray whose K upstream values are all exactly 0 is not traced.  ONE
+ * traversal (dloss/dalpha is the caller's), through the context's 64-B-per-particle gradient buffer and its flush exactly as
+ * grt_backward.  Float atomics: not bitwise reproducible; GRT_OPT_BWD_PLAIN_ATOMICS = 1 makes every lane issue its own (testing).
+ * A loss over more than K events of a ray takes a larger K: the pages of the forward are values, not a graph.
+ * Both: asynchronous on `stream` like grt_render; grt_last_kernel_ms reports the call's device time; a frame rendered after either
+ * call is bit-identical to one rendered before it; a view computes its scene's result.  With n = 0 rays or an empty window the calls
+ * return GRT_OK and write nothing; with no particles or an empty tree the forward writes "none", the backward nothing.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): everything
+ * grt_backward refuses (NULL p, no BVH, GRT_OPT_COUNTERS = 1, sh_degree_max > 3, t_min <= 0, a window outside the frame, a NULL ray
+ * buffer), meshes set (ray events are listed for Gaussian-only frames), max_events = 0, first + max_events overflowing 32 bits, no
+ * output (forward: out NULL or all five arrays NULL; backward: out NULL or pos, scale, quat and opacity all NULL), a NULL upstream,
+ * out->sh != NULL (colour does not depend on the listed quantities).  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks
+ * exceed 160 KiB, as in the backward.  Not computed: gradients through t_i, gradients with respect to rays or the camera, mesh frames. */
+typedef struct grt_ray_events {
+    uint32_t* id;    /* [K][N] */
+    float* t;        /* [K][N] */
+    float* alpha;    /* [K][N] */
+    uint32_t* count; /* [N] */
+    float* T_in;     /* [N] */
+    uint32_t first, max_events; /* K = max_events >= 1; first + K must not overflow */
+} grt_ray_events;
+GRT_API int grt_ray_events_frame(grt_ctx* ctx, const grt_params* p, const grt_ray_events* out, uint32_t x0, uint32_t y0, uint32_t x1,
+                                 uint32_t y1, void* stream);
+GRT_API int grt_ray_events_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_ray_events* out, void* stream);
+GRT_API int grt_backward_events_frame(grt_ctx* ctx, const grt_params* p, const float* d_grad_alpha, uint32_t first, uint32_t max_events,
+                                      const grt_gaussian_grads* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_events_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_alpha,
+                                     uint32_t first, uint32_t max_events, const grt_gaussian_grads* out, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
