@@ -1,6 +1,6 @@
 // grt_bwd.h — the device text the units that walk a ray's composited events share (grt_backward.hip, grt_backward_rays.hip,
-// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip, grt_picks.hip, grt_events.hip; DESIGN.md 5.8, 5.10, 5.11, 5.12, 5.17, 5.18, 5.19,
-// 5.20): the kernels' arguments, a
+// grt_backward_mesh.hip, grt_stats.hip, grt_stats_mesh.hip, grt_features.hip, grt_picks.hip, grt_events.hip; DESIGN.md 5.8, 5.10, 5.11, 5.12,
+// 5.17, 5.18, 5.19, 5.20, 5.21): the kernels' arguments, a
 // lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics, the
 // feature, the pick and the event-list kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
 // grouping of a wave's lanes by particle (wave_groups), the terms of one composited event (event_terms, and below one alpha: alpha_terms),
@@ -332,7 +332,8 @@ __device__ __forceinline__ bool load_upstream(const BwdArgs& b, size_t idx, bool
 // trip count, and a lane whose own condition is false idles inside them with `act` cleared.  The round itself is the per-lane
 // gps_round inside `if (act)`, with no wave operation in it.  A lane's rounds are bounded by lastT rising past the segment's end:
 // the ballot becomes zero.  A caller that loops around the sweep (passes) enters and leaves its loops the same way.
-// backward_body and k_backward_mesh hold this loop written out, statement for statement: a change here is a change there.
+// backward_body, k_backward_mesh and k_particle_stats_mesh hold this loop written out, statement for statement: a change here is a
+// change there.
 template <class OnSlot>
 __device__ __forceinline__ void sweep_events(const RenderArgs& a, uint32_t* stk, f3 o, f3 d, const rayinv& ri, float t_max, bool part, float& T,
                                              OnSlot&& on_slot)

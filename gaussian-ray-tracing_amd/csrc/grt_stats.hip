@@ -3,7 +3,8 @@
 // number of its composited events, over the rays of a window or of a ray buffer.
 //
 // k_particle_stats<MERGE> is ONE sweep_events call (grt_bwd.h) without colour: lane_ray gives the ray, one ray per lane, an 8x8 tile
-// per wave, every lane of the wave in step.  Per slot of the k-buffers the wave scatters through wave_groups as scatter<MERGE>
+// per wave, every lane of the wave in step.  Per slot of the k-buffers the wave scatters (stats_scatter, grt_stats.h: shared with the
+// mesh frames' unit grt_stats_mesh.hip) through wave_groups as scatter<MERGE>
 // does: of the lanes that hold the same particle the group's count is its size, its sum wave_sum, its peak wave_max (grt_wave.h), and
 // its leader issues one atomic per requested output; a lane alone with its particle issues its own.  MERGE = false
 // (GRT_OPT_BWD_PLAIN_ATOMICS = 1): every lane issues its own.  The atomics go straight into the caller's arrays: float add,
@@ -11,43 +12,12 @@
 #include <string>
 
 #include "grt_bwd.h"
+#include "grt_stats.h"
 
 namespace grt {
 namespace {
 
 static_assert(kBlock == kRoundBlock, "k_particle_stats runs gps_round (grt_kround.h): its per-lane stack stride is the launch block size");
-
-struct StatsArgs {
-    const float* ray_weight; // [pixels or rays] or null (= 1)
-    float* weight_sum;       // [n] by original id, or null
-    float* weight_max;       // [n] or null
-    uint32_t* count;         // [n] or null
-};
-
-// one atomic per requested output (the branches are wave-uniform: kernel arguments)
-__device__ __forceinline__ void stats_add(const StatsArgs& s, uint32_t id, float sum, float peak, uint32_t n)
-{
-    if (s.weight_sum) atomicAdd(s.weight_sum + id, sum);
-    if (s.weight_max) atomicMax(reinterpret_cast<unsigned int*>(s.weight_max) + id, __float_as_uint(peak)); // (peak >= 0: its bits order as it does)
-    if (s.count) atomicAdd(s.count + id, n);
-}
-
-// Called by the WHOLE wave (ev: this lane has an event of particle id with weight w = T alpha; ws = w_ray * w).
-template <bool MERGE>
-__device__ __forceinline__ void stats_scatter(const StatsArgs& s, bool ev, uint32_t id, float ws, float w, uint32_t lane)
-{
-    if (!MERGE) {
-        if (ev) stats_add(s, id, ws, w, 1u);
-        return;
-    }
-    const bool solo = wave_groups(ev, id, [&](uint32_t lid, bool mine, uint32_t n, uint32_t leader) {
-        float sum = 0.0f, peak = 0.0f;
-        if (s.weight_sum) sum = wave_sum(mine ? ws : 0.0f);
-        if (s.weight_max) peak = wave_max(mine ? w : 0.0f);
-        if (lane == leader) stats_add(s, lid, sum, peak, n);
-    });
-    if (solo) stats_add(s, id, ws, w, 1u);
-}
 
 template <bool MERGE>
 __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, const StatsArgs s)
@@ -73,7 +43,7 @@ __global__ __launch_bounds__(kBlock) void k_particle_stats(const RenderArgs a, c
     sweep_events(a, stk, o, d, mk_rayinv(o, d), a.p.t_max, live, T, [&](bool ev, uint32_t id, float Tb, float hitAlpha, uint64_t) {
         float w = 0.0f;
         if (ev) w = Tb * hitAlpha; // Tb: the transmittance before the event
-        stats_scatter<MERGE>(s, ev, id, wr * w, w, lane);
+        stats_scatter<MERGE, false>(s, ev, id, wr * w, w, 0.0f, 0.0f, lane);
     });
 }
 
@@ -102,6 +72,7 @@ static int launch(grt_ctx* c, const RenderArgs& a, const float* d_ray_weight, co
     StatsArgs sa;
     sa.ray_weight = d_ray_weight;
     sa.weight_sum = out->weight_sum; sa.weight_max = out->weight_max; sa.count = out->count;
+    sa.colour_sum = sa.colour_max = nullptr; // (mesh frames: grt_stats_mesh.hip)
     const void* fnk = c->opt_bwd_plain ? reinterpret_cast<const void*>(k_particle_stats<false>) : reinterpret_cast<const void*>(k_particle_stats<true>);
     void* args[2] = {const_cast<RenderArgs*>(&a), &sa};
     int rc = lane_launch(c, a, fnk, args, s, fn);

@@ -94,6 +94,13 @@ class ParticleStats(C.Structure):
     _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("count", C.c_void_p)]
 
 
+class ParticleStatsMesh(C.Structure):
+    """grt_particle_stats_mesh (include/grt.h): device pointers of the per-particle weight_sum / weight_max / count / colour_sum /
+    colour_max arrays, each may be NULL, and the iterations whose events are counted (1-based, inclusive; 0, 0 = all)."""
+    _fields_ = [("weight_sum", C.c_void_p), ("weight_max", C.c_void_p), ("count", C.c_void_p), ("colour_sum", C.c_void_p),
+                ("colour_max", C.c_void_p), ("step_first", C.c_uint32), ("step_last", C.c_uint32)]
+
+
 class PickOut(C.Structure):
     """grt_pick_out (include/grt.h): device pointers of one rule's id / t / weight arrays, each may be NULL."""
     _fields_ = [("id", C.c_void_p), ("t", C.c_void_p), ("weight", C.c_void_p)]
@@ -127,6 +134,7 @@ REASON_NONE, REASON_FIRST_BUILD, REASON_N_CHANGED, REASON_SET_CHANGED, REASON_OP
 
 GRAD_SHAPES = {"pos": (3,), "scale": (3,), "quat": (4,), "opacity": (), "sh": (16, 3)}
 STATS_OUTPUTS = ("weight_sum", "weight_max", "count")
+MESH_STATS_OUTPUTS = STATS_OUTPUTS + ("colour_sum", "colour_max")
 MAX_FEATURE_CHANNELS = 16  # GRT_MAX_FEATURE_CHANNELS
 PICK_NONE = 0xFFFFFFFF     # GRT_PICK_NONE
 PICK_RULES = ("first", "peak", "cross")
@@ -168,7 +176,7 @@ EXPORTS = [
     "grt_set_meshes", "grt_update_meshes", "grt_get_bvh_info", "grt_debug_bvh_depth", "grt_debug_copy_tree", "grt_debug_order_units",
     "grt_debug_order_scratch_bytes", "grt_debug_estimate_costs", "grt_debug_copy_schedule", "grt_render", "grt_render_tiles", "grt_assemble_tiles", "grt_render_rays", "grt_render_aux",
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
-    "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
+    "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_particle_stats_mesh_frame", "grt_particle_stats_mesh_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
     "grt_ray_events_frame", "grt_ray_events_rays", "grt_backward_events_frame", "grt_backward_events_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
@@ -230,6 +238,8 @@ def lib():
         L.grt_backward_rays_mesh.argtypes = [vp, C.POINTER(Params), vp, u64, vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_particle_stats_frame.argtypes = [vp, C.POINTER(Params), vp, C.POINTER(ParticleStats), u32, u32, u32, u32, vp]
         L.grt_particle_stats_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(ParticleStats), vp]
+        L.grt_particle_stats_mesh_frame.argtypes = [vp, C.POINTER(Params), vp, C.POINTER(ParticleStatsMesh), u32, u32, u32, u32, vp]
+        L.grt_particle_stats_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, C.POINTER(ParticleStatsMesh), vp]
         L.grt_ray_picks_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayPicks), u32, u32, u32, u32, vp]
         L.grt_ray_picks_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayPicks), vp]
         L.grt_ray_events_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayEvents), u32, u32, u32, u32, vp]
@@ -729,25 +739,49 @@ class Tracer:
         The tensors are allocated zeroed for `outputs`, or the call ACCUMULATES (add, max, add) into the tensors of `into` (its keys
         are the outputs computed; 'count' may be uint32 or int32): several views sum up into one dict.  count and weight_max are
         bitwise reproducible, weight_sum is not (float atomics)."""
+        return self._particle_stats("particle_stats", STATS_OUTPUTS, None, params, rays, ray_weight, window, into, outputs)
+
+    def particle_stats_mesh(self, params, rays=None, ray_weight=None, window=None, into=None, outputs=MESH_STATS_OUTPUTS, steps=None):
+        """grt_particle_stats_mesh_frame / grt_particle_stats_mesh_rays: particle_stats() of a frame whose rays bounce off the meshes
+        set on the tracer (include/grt.h) — the particles met behind a mirror or through glass are counted with the ones the camera
+        rays meet.  Beside 'weight_sum', 'weight_max' and 'count' (on w_i = T_i * alpha_i, ONE transmittance running through all of
+        a ray's segments) the dict holds 'colour_sum' and 'colour_max' on the colour weight c_s * w_i with which the particle's
+        radiance enters the pixel.  steps = (first, last): only the events of these iterations of the bounce loop are counted
+        (1-based, inclusive; last None = open; None = all): (1, 1) is what the camera rays meet directly, (2, None) what is met only
+        through a bounce.  Everything else is particle_stats(): ray_weight, window, `into` accumulating (add, max, add, add, max),
+        `outputs` choosing what is computed (without a colour output a ray is walked once, else twice).  On a tracer without meshes
+        count, weight_max and weight_sum are particle_stats()'s."""
+        if steps is None:
+            first, last = 0, 0
+        else:
+            first, last = steps
+            first, last = int(first), 0 if last is None else int(last)
+            if first < 0 or last < 0 or (steps[1] is not None and last == 0):
+                raise GrtError(f"particle_stats_mesh: steps must be (first, last) with 1 <= first <= last, or last None, not {tuple(steps)}")
+        return self._particle_stats("particle_stats_mesh", MESH_STATS_OUTPUTS, (first, last), params, rays, ray_weight, window, into, outputs)
+
+    def _particle_stats(self, who, names, steps, params, rays, ray_weight, window, into, outputs):
+        """The checks, the allocation and the call of particle_stats (steps None) and particle_stats_mesh."""
         t = self._torch
         dev = t.device("cuda", self.device)
         n = self._scene.n_particles if self._scene is not None else self.n_particles
         if into is None:
-            bad = [k for k in outputs if k not in STATS_OUTPUTS]
+            bad = [k for k in outputs if k not in names]
             if bad or not len(outputs):
-                raise GrtError(f"particle_stats: outputs must be a non-empty subset of {STATS_OUTPUTS}, not {tuple(outputs)}")
+                raise GrtError(f"{who}: outputs must be a non-empty subset of {names}, not {tuple(outputs)}")
             into = {k: t.zeros((n,), dtype=t.uint32 if k == "count" else t.float32, device=dev) for k in outputs}
         for k, v in into.items():
             ok_dt = (t.uint32, t.int32) if k == "count" else (t.float32,)
-            if k not in STATS_OUTPUTS or tuple(v.shape) != (n,) or v.dtype not in ok_dt or not v.is_contiguous() or v.device != dev:
-                raise GrtError(f"particle_stats: tensor '{k}' must be contiguous {'uint32 / int32' if k == 'count' else 'float32'} of shape "
+            if k not in names or tuple(v.shape) != (n,) or v.dtype not in ok_dt or not v.is_contiguous() or v.device != dev:
+                raise GrtError(f"{who}: tensor '{k}' must be contiguous {'uint32 / int32' if k == 'count' else 'float32'} of shape "
                                f"({n},) on {dev}")
-        ptrs = ParticleStats(*(into[k].data_ptr() if k in into and n else None for k in STATS_OUTPUTS))
+        fields = [into[k].data_ptr() if k in into and n else None for k in names]
+        ptrs = ParticleStats(*fields) if steps is None else ParticleStatsMesh(*fields, *steps)
         if not n:  # (an empty scene: nothing to write, and no pointer to hand over)
             return into
         if rays is not None:
             if rays.dim() != 2 or rays.shape[1] != 6:
-                raise GrtError(f"particle_stats: rays must have shape [n][6], not {tuple(rays.shape)}")
+                raise GrtError(f"{who}: rays must have shape [n][6], not {tuple(rays.shape)}")
             rays = rays.detach().to(dev, t.float32).contiguous()
             shape = (rays.shape[0],)
         else:
@@ -755,16 +789,18 @@ class Tracer:
         if ray_weight is not None:
             ray_weight = t.as_tensor(ray_weight).detach().to(dev, t.float32).contiguous()
             if tuple(ray_weight.shape) != shape:
-                raise GrtError(f"particle_stats: ray_weight must have shape {shape}, not {tuple(ray_weight.shape)}")
+                raise GrtError(f"{who}: ray_weight must have shape {shape}, not {tuple(ray_weight.shape)}")
         wp = ray_weight.data_ptr() if ray_weight is not None else None
+        L = lib()
         if rays is not None:
             if window is not None:
-                raise GrtError("particle_stats: rays and window exclude each other")
-            self._check(lib().grt_particle_stats_rays(self._h, C.byref(params), rays.data_ptr() if shape[0] else None, shape[0], wp,
-                                                      C.byref(ptrs), self._stream()))
+                raise GrtError(f"{who}: rays and window exclude each other")
+            fn = L.grt_particle_stats_rays if steps is None else L.grt_particle_stats_mesh_rays
+            self._check(fn(self._h, C.byref(params), rays.data_ptr() if shape[0] else None, shape[0], wp, C.byref(ptrs), self._stream()))
         else:
             x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
-            self._check(lib().grt_particle_stats_frame(self._h, C.byref(params), wp, C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+            fn = L.grt_particle_stats_frame if steps is None else L.grt_particle_stats_mesh_frame
+            self._check(fn(self._h, C.byref(params), wp, C.byref(ptrs), x0, y0, x1, y1, self._stream()))
         return into
 
     def ray_picks(self, params, rays=None, window=None, cross_T=0.5, picks=PICK_RULES, fields=PICK_FIELDS):

@@ -151,15 +151,22 @@ def render(tracer, params, pos, scale, quat, opacity, sh, rays=None, update="aut
     return _Render.apply(pos, scale, quat, opacity, sh, rays, cam_rays, tracer, params, update)
 
 
-def particle_stats(tracer, params, rays=None, ray_weight=None, into=None):
+def particle_stats(tracer, params, rays=None, ray_weight=None, into=None, steps=None):
     """Per-particle contribution statistics of the frame (or of `rays` [n][6]) under torch.no_grad(): a dict of 'weight_sum',
     'weight_max' (float32) and 'count' tensors [n_particles] on the tracer's GPU (Tracer.particle_stats; include/grt.h:
     grt_particle_stats_frame / grt_particle_stats_rays) — which particles the view composited and how strongly, for visibility
     masks, densification gates and pruning.  Like the backward it reads the scene the tracer HOLDS: call it right after
     grt_torch.render(tracer, ...), before the next upload to the same tracer.  ray_weight ([h][w] or [n]; None = 1) scales
     weight_sum, and a ray of weight exactly 0 is not traced; `into` accumulates several views into one dict.  Nothing here is
-    differentiable: the tensors carry no graph."""
+    differentiable: the tensors carry no graph.
+    With meshes set on the tracer, or with steps=(first, last) given, the call goes to Tracer.particle_stats_mesh (the way render
+    dispatches): the rays bounce as the frame's do, the particles met behind a mirror or through glass are counted too, and the
+    dict also holds 'colour_sum' and 'colour_max' on the weight with which a particle's radiance enters the pixel.  steps counts
+    only the events of these iterations of the bounce loop: (1, 1) what the camera rays meet directly, (2, None) what is met only
+    through a bounce."""
     with torch.no_grad():
+        if tracer.has_meshes or steps is not None:
+            return tracer.particle_stats_mesh(params, rays=rays, ray_weight=ray_weight, into=into, steps=steps)
         return tracer.particle_stats(params, rays=rays, ray_weight=ray_weight, into=into)
 
 

@@ -586,7 +586,7 @@ GRT_API int grt_backward_rays_mesh(grt_ctx* ctx, const grt_params* p, const floa
  * unchanged by a call, and a frame rendered after a call is bit-identical to one rendered before it.  Asynchronous on `stream` like
  * grt_render; grt_last_kernel_ms reports the call's device time.  A view computes the statistics of its scene.
  * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): meshes set
- * (statistics of mesh frames are not computed), GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a window outside the frame,
+ * (statistics of mesh frames: grt_particle_stats_mesh_frame / grt_particle_stats_mesh_rays, below), GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a window outside the frame,
  * sh_degree_max > 3, t_min <= 0.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB, as in the backward. */
 typedef struct {
     float* weight_sum;
@@ -597,6 +597,47 @@ GRT_API int grt_particle_stats_frame(grt_ctx* ctx, const grt_params* p, const fl
                                      const grt_particle_stats* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_particle_stats_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n,
                                     const float* d_ray_weight /* may be NULL */, const grt_particle_stats* out, void* stream);
+/* ---- per-particle contribution statistics of MESH frames: what a view sees through mirrors and glass ----
+ * The statistics above for a scene with meshes set (grt_set_meshes): rays bounce as grt_render / grt_render_aux trace them, and the
+ * particles met behind a bounce are counted with the ones met in front of it.  A ray runs iterations s = 1..S, as documented at
+ * grt_backward_mesh.  It has ONE event list with ONE running transmittance, T_1 = 1 and T_{i+1} = T_i (1 - alpha_i), cut into the
+ * segments of its iterations; the loop carries it across segments as the forward does, through `density`.  A COMPOSITED EVENT is
+ * exactly the mesh backward's.  For event i in segment s:
+ *     w_i  = T_i alpha_i        the plain statistics' weight, one float32 multiplication
+ *     cw_i = c_s w_i            the COLOUR WEIGHT, with which the particle's radiance L_i enters the pixel (dC/dL_i), where
+ *     c_s  = 1 - A_{s-1}            for a Gaussian pass (A: the accumulated alpha in front of the iteration),
+ *            D_S (1 - B_{S-1})      for the last pass (D_S: the density 1 - T behind the ray's last segment, B: the blocking),
+ *            1                      for a terminating GRT_NORMAL hit,
+ * c_s formed in float32 as the forward forms it and multiplied ONCE with w_i.  The two weights diverge behind a bounce: A sums
+ * cumulative densities and saturates long before T is spent, so a reflected particle can have a large w_i and a colour weight of 0.
+ * "Was met" reads count / weight_*; "matters to the image" reads colour_*.  Per particle j by ORIGINAL id, over the rays r:
+ *     weight_sum[j] += sum w_ray(r) * w_i      weight_max[j] = max(weight_max[j], max w_i)      count[j] += number of events
+ *     colour_sum[j] += sum w_ray(r) * cw_i     colour_max[j] = max(colour_max[j], max cw_i)
+ *   step_first, step_last   the iterations whose events are counted, 1-based, inclusive; 0, 0 = all; step_last = 0 leaves the range
+ *                  open.  Events outside the range are still composited (T and A run through them); they only enter no output.
+ *                  (1, 1): what the camera rays meet directly; (2, 0): what is met only through a bounce.
+ * Everything else is the plain call's contract: the outputs are ACCUMULATED (add, max, add, add, max) into the caller's arrays; each
+ * pointer may be NULL, all five NULL: GRT_ERR_INVALID; a ray of weight exactly 0 is not traced; weight_max and colour_max are updated
+ * by an unsigned-integer atomic max on the bit patterns of non-negative floats; count, weight_max and colour_max are BITWISE
+ * reproducible between calls, the two sums are not; GRT_OPT_BWD_PLAIN_ATOMICS applies; the context owns no buffer for this and a
+ * frame rendered after a call is bit-identical to one rendered before it; a view computes the statistics of its scene.  With neither
+ * colour output asked for a ray is walked once, else twice (D_S is known only at the end of the last segment).
+ * On a scene WITHOUT meshes a ray has one last pass: count, weight_max and weight_sum are the plain call's, cw_i = (1 - T_end) w_i.
+ * Refused with GRT_ERR_INVALID like the plain call, without its meshes row: GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a
+ * window outside the frame, sh_degree_max > 3, t_min <= 0; and p->type outside MIRROR/NORMAL/GLASS, step_first > step_last with
+ * step_last != 0.  GRT_ERR_LIMIT as in the backward.  Not computed on mesh frames: picks, event lists, feature channels. */
+typedef struct {
+    float* weight_sum;
+    float* weight_max;
+    uint32_t* count;
+    float* colour_sum;
+    float* colour_max;
+    uint32_t step_first, step_last;
+} grt_particle_stats_mesh;
+GRT_API int grt_particle_stats_mesh_frame(grt_ctx* ctx, const grt_params* p, const float* d_ray_weight /* may be NULL */,
+                                          const grt_particle_stats_mesh* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_particle_stats_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n,
+                                         const float* d_ray_weight /* may be NULL */, const grt_particle_stats_mesh* out, void* stream);
 /* ---- per-particle feature channels rendered through the Gaussians, with gradients (Gaussian-only frames) ----
  * The caller's own per-particle quantity — semantic or language embeddings, labels, an error or an age for a heat map, any learned
  * channel — composited with the renderer's weights, and the gradient back to it and to the Gaussians: feature-field distillation on
