@@ -152,6 +152,33 @@ __device__ __forceinline__ float proxy_sphere_cc(f3 o_g, float s)
     const float R = 1.2585f * s;
     return dot3(o_g, o_g) - R * R;
 }
+// The alpha sphere: the same pre-test against the sphere no ray outside of which the particle can change.  The proxy has inradius s =
+// sqrtf(2 logf(opacity / alpha_min)) in Gaussian space, so on its insphere response * opacity = alpha_min exactly: a ray whose closest
+// approach q = |p_g|^2 exceeds s^2 has hitAlpha <= alpha_min, and both its events with the icosahedron are no-ops of the compositing
+// step (shaders/tracer.cuh:361) whether it hits the icosahedron or not.  cc = |o_g|^2 - R_a^2 goes through proxy_sphere_maybe_pre as
+// the circumsphere's does.  The tile kernel's uncounted camera-ray instantiations use it (grt_tile.h); everything else, and every
+// counted frame, keeps the circumsphere: hit_evals counts the no-op events too.
+// The margin R_a^2 = s^2 (1 + kAlphaSphereRel) + kAlphaSphereAbs makes "pre-test false => fminf(0.99f, response_from() * opacity) <=
+// alpha_min" hold in float arithmetic (u = 2^-24):
+//   - s^2: opacity / alpha_min rounds by u relative, which logf turns into u ABSOLUTE (1.2e-7 in s^2, a relative 3e-4 of it at
+//     opacity = 1.0001 alpha_min); logf, sqrtf and the square add 4 u relative.                              <= 1.5e-7 + 3e-7 s^2
+//   - exp_nonpos (1 ulp) and the product with the opacity: 3 u relative in alpha, as if q were 4e-7 smaller.  <= 4e-7
+//   - response_from goes back through world space: pos = o + d t rounds by u (|o| + |t d|), mu - pos inherits it, and A takes it to
+//     u |A| (|o| + |mu| + |t|) <= u (|o| + |mu|) / scale_min + u |o_g| scale_max / scale_min; the matvec itself adds 3 u |A| |mu - pos|
+//     <= 3 u sqrt(q) scale_max / scale_min.  With e that error of p_g, q moves by 2 sqrt(q) e.  For axis ratios up to 1e3, world
+//     coordinates up to 1e3 scale_min and sqrt(q) = s <= 3.4 that is <= 2 s u 1e3 (|o_g| + 3 s + 2) = 1.2e-4 s (|o_g| + 3 s + 2).
+//   - the pre-test's own dot products: 3 u |o_g|^2 each for |o_g|^2 and b^2 / aa; the existing slack 4e-6 b^2 covers them with 3.6e-6
+//     |o_g|^2 to spare, which also outgrows the response term above once |o_g| > 33 s.
+//   Below |o_g| = 33 s the response term is <= 1.2e-4 s (36 s + 2), at most 4.4e-3 s^2 + 2.4e-4 s before the slack's share is taken off
+//   — the bound adds three worst cases that no one ray meets together.  tests/test_alpha_sphere.py measures, on 4e6 pairs drawn on the
+//   boundary (axis ratios to 1e3, |o_g| to 1e4, opacity down to nextafter(alpha_min)), a largest needed margin of 3.8e-4 s^2 for s^2 >
+//   0.01 and of 6.2e-6 absolute below: the constants leave a factor of five on the first and, with the relative part, on the second.
+constexpr float kAlphaSphereRel = 2e-3f;
+constexpr float kAlphaSphereAbs = 1e-5f;
+__device__ __forceinline__ float proxy_alpha_sphere_cc(f3 o_g, float s)
+{
+    return dot3(o_g, o_g) - ((s * s) * (1.0f + kAlphaSphereRel) + kAlphaSphereAbs);
+}
 __device__ __forceinline__ bool proxy_sphere_maybe_pre(f3 o_g, float cc, f3 d_g)
 {
     const float b = dot3(o_g, d_g), aa = dot3(d_g, d_g);

@@ -36,8 +36,11 @@ __global__ void k_eye_records(const float4* __restrict__ rec, uint32_t m, float 
 
 // Wide eye records for the tile kernel, 64 B: the same (o_g, cc) plus the ten slab projections of o_g
 // (slab_project, grt_device.h) that the exact proxy test otherwise forms on every lane from wave-uniform inputs:
-//   (o_g.x o_g.y o_g.z cc) (a0 a1 a2 a3) (a4 a5 a6 a7) (a8 a9 0 0)
-__global__ void k_eye_records_wide(const float4* __restrict__ rec, uint32_t m, float ex, float ey, float ez,
+//   (o_g.x o_g.y o_g.z cc) (a0 a1 a2 a3) (a4 a5 a6 a7) (a8 a9 cc_a 0)
+// cc_a = |o_g|^2 - R_a^2 of the alpha sphere (proxy_alpha_sphere_cc): the pre-test value of the uncounted instantiations, which skip
+// the particles no ray of the tile can see above alpha_min; counted frames read cc.  alpha_sphere = 0: the frame's alpha_min lies below
+// the one the proxies were sized with, the insphere is then not the frame's alpha sphere, and cc_a = cc.
+__global__ void k_eye_records_wide(const float4* __restrict__ rec, uint32_t m, float ex, float ey, float ez, uint32_t alpha_sphere,
                                    float4* __restrict__ erec)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -52,10 +55,11 @@ __global__ void k_eye_records_wide(const float4* __restrict__ rec, uint32_t m, f
     float pa[10];
     slab_project(o_g, pa);
     float4* e = erec + (size_t)j * 4;
-    e[0] = make_float4(o_g.x, o_g.y, o_g.z, proxy_sphere_cc(o_g, r0.w));
+    const float cc = proxy_sphere_cc(o_g, r0.w);
+    e[0] = make_float4(o_g.x, o_g.y, o_g.z, cc);
     e[1] = make_float4(pa[0], pa[1], pa[2], pa[3]);
     e[2] = make_float4(pa[4], pa[5], pa[6], pa[7]);
-    e[3] = make_float4(pa[8], pa[9], 0.0f, 0.0f);
+    e[3] = make_float4(pa[8], pa[9], alpha_sphere ? proxy_alpha_sphere_cc(o_g, r0.w) : cc, 0.0f);
 }
 
 // Cold-start scheduling estimate: how many particle centres project into each 8x8 tile (scheduling unit).  Used ONLY to
@@ -756,22 +760,29 @@ static int overflow_pool(grt_ctx* c, RenderArgs& a, hipStream_t s, bool tile_ker
     }
     return GRT_OK;
 }
+// The alpha-sphere pre-test (grt_device.h: proxy_alpha_sphere_cc) rests on the proxies' inradius being the frame's alpha sphere: true
+// when the frame's alpha_min is the one the scene was built with, or larger (the sphere is then merely not tight).  A frame with a
+// smaller alpha_min keeps the circumsphere: its eye records say so, and its four-way parts stay on the camera-ray kernel.
+static bool alpha_sphere_ok(const grt_ctx* c, const grt_params& p) { return p.alpha_min >= scene_of(c)->alpha_min; }
 // 9. wave-per-tile kernels on camera rays: refresh the eye records when the eye moved (part of the timed frame)
 static void refresh_eye_records(grt_ctx* c, RenderArgs& a, hipStream_t s, bool tile_kernel)
 {
     const grt_ctx* sc = scene_of(c);
     const uint32_t m = sc->gbvh.n_prims;
     const bool wide = tile_kernel;
-    if (!c->erec_valid || c->erec_is_wide != wide || memcmp(c->erec_eye, a.p.eye, sizeof(c->erec_eye)) != 0) {
+    const bool tight = alpha_sphere_ok(c, a.p); // (wide records only: the narrow ones hold no alpha-sphere value)
+    if (!c->erec_valid || c->erec_is_wide != wide || (wide && c->erec_alpha_sphere != tight) ||
+        memcmp(c->erec_eye, a.p.eye, sizeof(c->erec_eye)) != 0) {
         if (wide)
             hipLaunchKernelGGL(k_eye_records_wide, dim3((m + 255) / 256), dim3(256), 0, s, sc->d_rec, m, a.p.eye[0],
-                               a.p.eye[1], a.p.eye[2], c->d_erec_wide);
+                               a.p.eye[1], a.p.eye[2], tight ? 1u : 0u, c->d_erec_wide);
         else
             hipLaunchKernelGGL(k_eye_records, dim3((m + 255) / 256), dim3(256), 0, s, sc->d_rec, m, a.p.eye[0], a.p.eye[1],
                                a.p.eye[2], c->d_erec);
         memcpy(c->erec_eye, a.p.eye, sizeof(c->erec_eye));
         c->erec_valid = true;
         c->erec_is_wide = wide;
+        c->erec_alpha_sphere = tight;
     }
     a.erec = wide ? c->d_erec_wide : c->d_erec;
 }
@@ -792,7 +803,7 @@ static int tile_tuning(grt_ctx* c, RenderArgs& a, hipStream_t s, bool tile_kerne
     a.tile_reserve = c->opt_tile_reserve >= 0 ? (uint32_t)c->opt_tile_reserve : (sc->has_pieces ? 24u : 16u);
     a.tile_band_abs = (float)c->opt_band_abs / 64.0f * sc->gm_diag;
     a.tile_prio_div = (uint32_t)c->opt_tile_prio;
-    a.quad_parts = (quad_parts_ok(c, a.n_units) && tile_kernel && c->parts_ok && a.mode != 2 && a.order && a.n_launch && c->qparts_valid) ? 1u : 0u;
+    a.quad_parts = (quad_parts_ok(c, a.n_units) && alpha_sphere_ok(c, a.p) && tile_kernel && c->parts_ok && a.mode != 2 && a.order && a.n_launch && c->qparts_valid) ? 1u : 0u;
     a.qparts = c->d_qparts; a.qpart_count = c->d_qpcount;
     // the list's length when the host knows it (a frame tail that ran behind the list's making has copied it to the pinned word; frames of
     // a standing view keep their order and their list, so frames queued without a host synchronisation between them know it too): a launch

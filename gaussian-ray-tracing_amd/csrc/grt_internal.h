@@ -368,6 +368,7 @@ struct grt_ctx {
     float4* d_erec_wide = nullptr; // 64-B eye records of the tile kernel (k_eye_records_wide)
     size_t cap_erec_wide = 0, cap_erec = 0;
     bool erec_is_wide = false;
+    bool erec_alpha_sphere = false; // the wide records' cc_a is the alpha sphere's (else the circumsphere's: alpha_sphere_ok, grt_frame.hip)
     float erec_eye[3] = {0, 0, 0};
     bool erec_valid = false;
     size_t cap_rec = 0;

@@ -1227,7 +1227,12 @@ __global__ __launch_bounds__(kWG, kWavesPerSimd) void k_render_tile_aux(const Re
                         // A (o - mu): from the eye record (wave-uniform), or per lane for a bundle / a quad's own particle (the very operation
                         // sequence the eye records were made with: the same bits)
                         const f3 o_g = (BUNDLE || QUAD) ? matvec(A, sub3(o, mu)) : mk3(e0.x, e0.y, e0.z);
-                        const float cc_ = (BUNDLE || QUAD) ? proxy_sphere_cc(o_g, r0.w) : e0.w;
+                        // the pre-test's sphere.  Camera rays of an uncounted frame: the alpha sphere (grt_device.h: proxy_alpha_sphere_cc; the
+                        // third float of the eye record's last quarter), so that a trip whose rays all pass the particle at alpha <= alpha_min
+                        // — events that change nothing — ends at the pre-test.  Counted frames run the reference's full event stream
+                        // (hit_evals counts the no-op events) on the circumsphere; so do the bundles (MODE 1, 2), left as they were.
+                        const float cc_ = BUNDLE ? proxy_sphere_cc(o_g, r0.w)
+                                                 : (QUAD ? (COUNT ? proxy_sphere_cc(o_g, r0.w) : proxy_alpha_sphere_cc(o_g, r0.w)) : (COUNT ? e0.w : e3.z));
                         const f3 d_g = matvec(A, d);
                         {   // conservative sphere pre-test (proxy_sphere_maybe_pre) as lane masks
                             const float b_ = dot3(o_g, d_g), aa_ = dot3(d_g, d_g);

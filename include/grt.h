@@ -134,7 +134,11 @@ typedef struct {
     uint32_t overflow_demand;     /* the demand the pool follows: median of what the last eight frames read back asked for */
 } grt_memory_info;
 
-enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_counters */,
+enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_counters.  A counted frame runs the reference's full event
+                               stream: hit_evals counts every consumed icosahedron event, those with alpha <= alpha_min included.
+                               An uncounted camera-ray frame of the tile kernel skips the particles none of a tile's rays passes
+                               inside the alpha sphere (response x opacity = alpha_min): events that change nothing.  The pixels
+                               are the same bytes either way; counted frames are never the timed ones */,
        GRT_OPT_KERNEL = 2   /* 0 = auto: camera-ray frames on the tile kernel (csrc/grt_tile.h: BVH culling per child box
                                against the tile frustum; also stage 2 of the wavefront pipeline of mesh frames) — or on the
                                streaming kernel when the BVH was built with GRT_OPT_LEAF_MAX > 4; ray buffers on the per-lane kernel.
