@@ -1,6 +1,6 @@
 // grt_bwd.h — the device text the units that walk a ray's composited events share (grt_backward.hip, grt_backward_rays.hip,
-// grt_backward_mesh.hip, grt_stats.hip, grt_stats_mesh.hip, grt_features.hip, grt_picks.hip, grt_events.hip; DESIGN.md 5.8, 5.10, 5.11, 5.12,
-// 5.17, 5.18, 5.19, 5.20, 5.21): the kernels' arguments, a
+// grt_backward_mesh.hip, grt_stats.hip, grt_stats_mesh.hip, grt_features.hip, grt_picks.hip, grt_events.hip, grt_segments.hip; DESIGN.md 5.8,
+// 5.10, 5.11, 5.12, 5.17, 5.18, 5.19, 5.20, 5.21, 5.22): the kernels' arguments, a
 // lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics, the
 // feature, the pick and the event-list kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
 // grouping of a wave's lanes by particle (wave_groups), the terms of one composited event (event_terms, and below one alpha: alpha_terms),

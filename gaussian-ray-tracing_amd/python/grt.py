@@ -118,6 +118,17 @@ class RayEvents(C.Structure):
                 ("first", C.c_uint32), ("max_events", C.c_uint32)]
 
 
+class Segments(C.Structure):
+    """grt_segments (include/grt.h): device pointers of the per-ray t_near / t_far / T_in arrays [N], each may be NULL (p->t_min,
+    p->t_max, 1 for every ray)."""
+    _fields_ = [("t_near", C.c_void_p), ("t_far", C.c_void_p), ("T_in", C.c_void_p)]
+
+
+class SegmentOut(C.Structure):
+    """grt_segment_out (include/grt.h): device pointers of radiance [N][3] and T_out / depth / count [N], each may be NULL, not all."""
+    _fields_ = [("radiance", C.c_void_p), ("T_out", C.c_void_p), ("depth", C.c_void_p), ("count", C.c_void_p)]
+
+
 class FeatureGrads(C.Structure):
     """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
@@ -142,6 +153,7 @@ PICK_FIELDS = ("id", "t", "weight")
 FEATURE_GROUPS = ("pos", "scale", "quat", "opacity", "feat")
 EVENT_FIELDS = ("id", "t", "alpha", "count", "T_in")
 EVENT_GROUPS = ("pos", "scale", "quat", "opacity")
+SEGMENT_OUTPUTS = ("radiance", "T_out", "depth", "count")
 
 
 class Mesh(C.Structure):
@@ -178,6 +190,7 @@ EXPORTS = [
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
     "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_particle_stats_mesh_frame", "grt_particle_stats_mesh_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
     "grt_ray_events_frame", "grt_ray_events_rays", "grt_backward_events_frame", "grt_backward_events_rays",
+    "grt_trace_segments_frame", "grt_trace_segments_rays", "grt_backward_segments_frame", "grt_backward_segments_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
@@ -246,6 +259,10 @@ def lib():
         L.grt_ray_events_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayEvents), vp]
         L.grt_backward_events_frame.argtypes = [vp, C.POINTER(Params), vp, u32, u32, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
         L.grt_backward_events_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, u32, C.POINTER(GaussianGrads), vp]
+        L.grt_trace_segments_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(Segments), C.POINTER(SegmentOut), u32, u32, u32, u32, vp]
+        L.grt_trace_segments_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(Segments), C.POINTER(SegmentOut), vp]
+        L.grt_backward_segments_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(Segments), vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
+        L.grt_backward_segments_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(Segments), vp, vp, C.POINTER(GaussianGrads), vp]
         L.grt_render_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, vp]
         L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
         L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
@@ -919,6 +936,94 @@ class Tracer:
         else:
             self._check(lib().grt_backward_events_frame(self._h, C.byref(params), grad_alpha.data_ptr(), first, K, C.byref(ptrs),
                                                         x0, y0, x1, y1, self._stream()))
+        return into
+
+    def _segment_inputs(self, what, params, rays, t_near, t_far, T_in, window):
+        """rays [n][6] (or None) as a contiguous float32 tensor on the tracer's GPU, the shape of one output plane, the window, and
+        the three per-ray inputs as contiguous float32 tensors of that shape (a scalar is expanded on the device; None stays None: the
+        call's default) with their Segments structure."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        if rays is not None:
+            if window is not None:
+                raise GrtError(f"{what}: rays and window exclude each other")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"{what}: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        keep = []
+        for name, v in (("t_near", t_near), ("t_far", t_far), ("T_in", T_in)):
+            if v is None:
+                keep.append(None)
+            elif t.is_tensor(v) and v.dim() > 0:
+                if tuple(v.shape) != shape:
+                    raise GrtError(f"{what}: {name} must be a scalar or have shape {list(shape)}, not {tuple(v.shape)}")
+                keep.append(v.detach().to(dev, t.float32).contiguous())
+            else:
+                keep.append(t.full(shape, float(v), dtype=t.float32, device=dev))
+        seg = Segments(*(x.data_ptr() if x is not None else None for x in keep))
+        return rays, shape, (window if window else (0, 0, params.width, params.height)), dev, keep, seg
+
+    def trace_segments(self, params, rays=None, t_near=None, t_far=None, T_in=None, window=None, outputs=SEGMENT_OUTPUTS):
+        """grt_trace_segments_frame / grt_trace_segments_rays (rays [n][6] given): the reference's trace() for one segment [t_near,
+        t_far] of every ray, entered with the transmittance T_in -> dict of torch tensors on the tracer's GPU: 'radiance' [n][3] or
+        [h][w][3] (R = sum T_i alpha_i L_i, NOT multiplied by the opacity), 'T_out' (T_in prod (1 - alpha_i)), 'depth' (sum T_i alpha_i
+        t_i) and 'count' (uint32) [n] or [h][w]; include/grt.h.  t_near, t_far, T_in: tensors of that shape, scalars (expanded on the
+        device) or None (params.t_min, params.t_max, 1).  A ray whose range is empty, reversed, not positive or not finite, or whose
+        T_in is not above minTransmittance, is untraced: zeros, and T_out a bit copy of T_in.  Outside a window the tensors hold 0 and
+        T_in's values.  Bitwise reproducible; backward_segments takes dloss/dradiance and dloss/dT_out back."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, keep, seg = self._segment_inputs("trace_segments", params, rays, t_near, t_far, T_in, window)
+        outputs = tuple(outputs)
+        if not outputs or any(k not in SEGMENT_OUTPUTS for k in outputs):
+            raise GrtError(f"trace_segments: outputs must be a non-empty subset of {SEGMENT_OUTPUTS}, not {outputs}")
+        make = {"radiance": lambda: t.zeros(shape + (3,), dtype=t.float32, device=dev),
+                "T_out": lambda: keep[2].clone() if keep[2] is not None else t.ones(shape, dtype=t.float32, device=dev),
+                "depth": lambda: t.zeros(shape, dtype=t.float32, device=dev),
+                "count": lambda: t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32)}
+        out = {k: make[k]() for k in SEGMENT_OUTPUTS if k in outputs}
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if not n or not shape[0] or not shape[-1]:  # (an empty scene or no ray: every element is untraced already)
+            return out
+        ptrs = SegmentOut(*(out[k].data_ptr() if k in out else None for k in SEGMENT_OUTPUTS))
+        if rays is not None:
+            self._check(lib().grt_trace_segments_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], C.byref(seg), C.byref(ptrs),
+                                                      self._stream()))
+        else:
+            self._check(lib().grt_trace_segments_frame(self._h, C.byref(params), C.byref(seg), C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return out
+
+    def backward_segments(self, params, grad_radiance, grad_T_out=None, rays=None, t_near=None, t_far=None, T_in=None, window=None,
+                          into=None, groups=None):
+        """grt_backward_segments_frame / grt_backward_segments_rays: grad_radiance [n][3] or [h][w][3] and grad_T_out [n] or [h][w]
+        (None: zero) hold dloss/dR and dloss/dT_out of the segments trace_segments traced (same params, rays / window, t_near, t_far,
+        T_in) -> dict of torch tensors pos, scale, quat, opacity, sh: the gradients with respect to the uploaded Gaussians, allocated
+        zeroed for `groups` (default: all five) or ACCUMULATED into the tensors of `into` (its keys are the groups computed).  No
+        forward outputs are passed; a ray whose four upstream values are exactly 0 is not traced.  Not bitwise reproducible (float
+        atomics); include/grt.h."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, keep, seg = self._segment_inputs("backward_segments", params, rays, t_near, t_far, T_in, window)
+        if not t.is_tensor(grad_radiance) or tuple(grad_radiance.shape) != shape + (3,):
+            raise GrtError(f"backward_segments: grad_radiance must be a tensor of shape {list(shape + (3,))}")
+        if grad_T_out is not None and tuple(grad_T_out.shape) != shape:
+            raise GrtError(f"backward_segments: grad_T_out must have shape {list(shape)}, not {tuple(grad_T_out.shape)}")
+        g_R = grad_radiance.detach().to(dev, t.float32).contiguous()
+        g_T = grad_T_out.detach().to(dev, t.float32).contiguous() if grad_T_out is not None else None
+        if (into is not None and not into) or (into is None and groups is not None and not len(groups)):
+            raise GrtError("backward_segments: no gradient group asked for")
+        into, ptrs = self._grad_buffers(into, groups, dev)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if not n or not g_R.numel():
+            return into
+        if rays is not None:
+            self._check(lib().grt_backward_segments_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], C.byref(seg), g_R.data_ptr(),
+                                                         g_T.data_ptr() if g_T is not None else None, C.byref(ptrs), self._stream()))
+        else:
+            self._check(lib().grt_backward_segments_frame(self._h, C.byref(params), C.byref(seg), g_R.data_ptr(),
+                                                          g_T.data_ptr() if g_T is not None else None, C.byref(ptrs), x0, y0, x1, y1,
+                                                          self._stream()))
         return into
 
     def _feature_inputs(self, what, params, feat, rays, window):

@@ -32,6 +32,11 @@ says which particle every ray of that scene sees first, strongest and where its 
 
 hands out every ray's own list of composited events; `alpha` carries the graph, so any per-ray loss written in torch
 on the events' alpha and distances is differentiable with respect to the four geometry tensors.
+
+    R, T_out, depth, count = grt_torch.trace_segments(tracer, params, rays, t_near, t_far, T_in, gaussians=(pos, scale, quat, opacity, sh))
+
+traces ONE segment of every ray with a range and an entering transmittance per ray: the plain radiance and the
+transmittance behind it, differentiable with respect to the five tensors and to T_in — a depth-buffer composite or a bounce loop in torch.
 """
 import numpy as np
 import torch
@@ -301,3 +306,93 @@ def render_features(tracer, params, feat, rays=None, geometry=None):
                 raise ValueError(f"grt_torch.render_features: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
                                  f"not {tuple(t.shape)}")
     return _RenderFeatures.apply(feat, *geo, rays, tracer, params)
+
+
+class _TraceSegments(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, scale, quat, opacity, sh, T_in, rays, t_near, t_far, window, tracer, params):
+        # pos .. sh: the tensors of the tracer's last upload: only the carriers of the gradients
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.params, ctx.window = tracer, params, window
+        ctx.rays = rays.detach() if rays is not None else None
+        ctx.range = tuple(x.detach() if torch.is_tensor(x) else x for x in (t_near, t_far))
+        ctx.like = tuple((t.device, t.dtype) for t in (pos, scale, quat, opacity, sh))
+        T0 = T_in.detach() if torch.is_tensor(T_in) else T_in
+        out = tracer.trace_segments(params, rays=ctx.rays, t_near=ctx.range[0], t_far=ctx.range[1], T_in=T0, window=window)
+        ctx.T_like = (T_in.device, T_in.dtype, tuple(T_in.shape)) if torch.is_tensor(T_in) else None
+        T0 = T0.to(out["T_out"].device, torch.float32).expand(out["T_out"].shape) if torch.is_tensor(T0) else T0
+        ctx.T_scalar = None if torch.is_tensor(T0) else T0
+        ctx.save_for_backward(out["radiance"], out["T_out"], *((T0,) if torch.is_tensor(T0) else ()))
+        ctx.mark_non_differentiable(out["depth"], out["count"])
+        return out["radiance"], out["T_out"], out["depth"], out["count"]
+
+    @staticmethod
+    def backward(ctx, g_R, g_T, g_depth, g_count):
+        R, T_out, *rest = ctx.saved_tensors
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("pos", "scale", "quat", "opacity", "sh")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:5]) if want]
+        g_R = torch.zeros_like(R) if g_R is None else g_R.to(R.device, torch.float32)
+        g_T = torch.zeros_like(T_out) if g_T is None else g_T.to(R.device, torch.float32)
+        out = (None,) * 5
+        if groups:
+            T0 = rest[0] if rest else ctx.T_scalar
+            g = tr.backward_segments(ctx.params, g_R, g_T, rays=ctx.rays, t_near=ctx.range[0], t_far=ctx.range[1], T_in=T0,
+                                     window=ctx.window, groups=groups)
+            out = tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like))
+        g_Tin = None
+        if ctx.needs_input_grad[5]:
+            # with the event set fixed R and T_out are linear in T_in; an untraced ray hands T_in through to T_out
+            T0 = rest[0]
+            traced = T0 > ctx.params.minTransmittance
+            lin = ((g_R * R).sum(-1) + g_T * T_out) / torch.where(traced, T0, torch.ones_like(T0))
+            g_Tin = torch.where(traced, lin, g_T)
+            dev, dt, shape = ctx.T_like
+            g_Tin = (g_Tin.sum() if shape == () else g_Tin).reshape(shape).to(dev, dt)
+        return out + (g_Tin,) + (None,) * 6
+
+
+def trace_segments(tracer, params, rays, t_near=None, t_far=None, T_in=None, gaussians=None, window=None):
+    """(radiance, T_out, depth, count) of one segment [t_near, t_far] of every ray, entered with the transmittance T_in
+    (Tracer.trace_segments; include/grt.h: grt_trace_segments_frame / _rays): the reference's trace() itself, for
+    compositing the Gaussians against a depth buffer, for a bounce loop written in torch (an analytic mirror: segment 1 on [t_min,
+    t_hit], the reflected rays entering segment 2 with T_in = T_out of segment 1, the image R1 + R2) and for the plain volumetric colour
+    sum w_i L_i.  rays [n][6], or None for the camera frame of `params` (its `window`); t_near, t_far, T_in: tensors [n] / [h][w],
+    scalars or None (params.t_min, params.t_max, 1).
+    Without `gaussians` it is the plain call under torch.no_grad().  With gaussians=(pos, scale, quat, opacity, sh) radiance and T_out
+    carry the graph: differentiable with respect to those five through the kernel (grt_backward_segments_*), and with respect to a
+    T_in tensor in torch — with the event set fixed R and T_out are linear in T_in, so grad_T_in = (g_R . R + g_T T_out) / T_in where
+    T_in > minTransmittance and g_T elsewhere (an untraced ray hands T_in through).  depth and count carry NO gradient, and neither
+    do the distances: `rays`, `t_near` or `t_far` that require grad raise ValueError.
+    It traces the scene the tracer HOLDS and uploads nothing, like render_features: grt_torch.render(tracer, ...) followed by
+    grt_torch.trace_segments(tracer, ...) can share one loss.backward().  The `gaussians` tensors only carry the gradient — they must
+    be the tensors of the tracer's last upload, their shapes are checked against the tracer's particle count and their values are not
+    read.  The backward raises GrtError when the tracer has received another upload since the forward.  A tracer with meshes:
+    ValueError (trace() is the Gaussian-only call)."""
+    if tracer.has_meshes:
+        raise ValueError("grt_torch.trace_segments: meshes are set on this tracer; trace() is the Gaussian-only call")
+    for name, t in (("rays", rays), ("t_near", t_near), ("t_far", t_far)):
+        if torch.is_tensor(t) and t.requires_grad:
+            raise ValueError(f"grt_torch.trace_segments: gradients with respect to {name} are not computed (distances and rays are data); "
+                             f"detach {name}")
+    if gaussians is None:
+        if torch.is_tensor(T_in) and T_in.requires_grad:
+            raise ValueError("grt_torch.trace_segments: a T_in that requires grad needs gaussians=(pos, scale, quat, opacity, sh)")
+        with torch.no_grad():
+            out = tracer.trace_segments(params, rays=rays, t_near=t_near, t_far=t_far, T_in=T_in, window=window)
+        return tuple(out[k] for k in grt.SEGMENT_OUTPUTS)
+    gs = tuple(gaussians)
+    scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene)
+    n = scene.n_particles
+    want = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,), "sh": (n, 16, 3)}
+    if len(gs) != 5 or any(not torch.is_tensor(t) for t in gs):
+        raise ValueError("grt_torch.trace_segments: gaussians must be five tensors (pos, scale, quat, opacity, sh)")
+    for (name, shape), t in zip(want.items(), gs):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"grt_torch.trace_segments: gaussians tensor '{name}' must have shape {shape} (the tracer's last upload), "
+                             f"not {tuple(t.shape)}")
+    return _TraceSegments.apply(*gs, T_in, rays, t_near, t_far, window, tracer, params)

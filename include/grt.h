@@ -795,6 +795,65 @@ GRT_API int grt_backward_events_frame(grt_ctx* ctx, const grt_params* p, const f
                                       const grt_gaussian_grads* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_backward_events_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_alpha,
                                      uint32_t first, uint32_t max_events, const grt_gaussian_grads* out, void* stream);
+/* ---- ray segments: per-ray range and carried transmittance, with gradients ----
+ * Every call above renders a WHOLE ray: one t_min / t_max for all rays, transmittance 1 at the start, the reference's pixel rad * A.
+ * These calls are the reference's trace() itself (shaders/tracer.cuh:328-373): ONE segment [t_near, t_far] of every ray, entered with
+ * the transmittance T_in the ray's earlier segments left, returning the plain radiance and the transmittance behind it.  With them a
+ * caller composites the Gaussians against a depth buffer of other geometry (the ray clipped to [t_min, z], the surface entering with
+ * T_out), writes a bounce loop of its own (an analytic mirror, another BRDF, a portal, a shadow ray: the reflected ray starts at
+ * T_in = T_out of the segment before), or takes the plain volumetric colour sum_i w_i L_i that rgbf = rad * A cannot be divided into.
+ * INPUT.  grt_segments: three device arrays [N] float32, each may be NULL (the default for every ray: p->t_min, p->t_max, 1); seg itself
+ * may be NULL (all three defaults).  When an array is given, p->t_min / p->t_max are not read for it.  p->max_bounces is not looked at:
+ * trace() has no bounce.  N = width * height for a frame (element py * width + px), n for a ray buffer.
+ * FORWARD.  For ray r with a = t_near[r], b = t_far[r], T0 = T_in[r] the events are exactly those trace() composites on [a, b] when it
+ * is entered with transmittance T0: key order, entry and exit hits, alpha_min < alpha_i, the 0.99 clamp, T_i = T0 prod_{j<i} (1 -
+ * alpha_j), the walk going on while T > minTransmittance (compared with the running T, so T0 counts) and the last distance <= b.
+ *     radiance [N][3]  R = sum_i T_i alpha_i L_i, accumulated as the frame does: R = R + (L T) alpha
+ *     T_out    [N]     T0 prod_i (1 - alpha_i)
+ *     depth    [N]     sum_i T_i alpha_i t_i (t_i: the event's key distance, in units of |d|), (T alpha) t added before T is updated
+ *     count    [N]     composited events
+ * With the defaults count, depth and 1 - T_out equal grt_render_rays_aux's bit for bit, and R (1 - T_out) its rgbf.
+ * A ray is UNTRACED when |d| > 0.1 fails, a > 0 fails (keys need positive distances), a <= b fails or b is not finite, T0 >
+ * minTransmittance fails — a NaN in any of the three fails these tests —, the tree is empty, or a fisheye pixel has no ray.  It writes
+ * R = 0, depth = 0, count = 0 and T_out as a BIT COPY of T_in (a NaN's payload included).  Every element of the buffer or of the window
+ * is WRITTEN exactly once per requested array; pixels outside the window are untouched.  Each output may be NULL, not all.  No atomic, no
+ * wave operation and no buffer of the context: the call is BITWISE reproducible and windows tile a frame bit for bit.
+ * BACKWARD.  d_grad_radiance [N][3] = dloss/dR and d_grad_T_out [N] = dloss/dT_out (NULL: zero).  The call ADDS
+ *     g_R . dR/dtheta + g_T dT_out/dtheta        theta in pos, scale, quat, opacity, sh
+ * into the caller's arrays (grt_gaussian_grads; the caller zeroes them), every discrete decision held fixed as in grt_backward.  It takes
+ * no forward outputs: its first sweep recomputes R and T_out.  A ray whose four upstream values are exactly 0 is not traced; nothing goes
+ * into opacity or geometry where the 0.99 clamp binds.  Through the context's gradient buffer and its flush exactly as grt_backward.
+ * Float atomics: not bitwise reproducible; GRT_OPT_BWD_PLAIN_ATOMICS = 1 makes every lane issue its own (testing).  The distances
+ * (t_near, t_far, t_i in depth) and the event set are DATA: no gradients through them, through the rays, or through depth / count.  With
+ * the event set fixed R and T_out are linear in T_in, so dloss/dT_in = (g_R . R + g_T T_out) / T_in is the caller's to form.
+ * Both: asynchronous on `stream` like grt_render; grt_last_kernel_ms reports the call's device time; a view computes its scene's
+ * result.  With n = 0 rays or an empty window the calls return GRT_OK and write nothing; with no particles or an empty tree the forward
+ * writes untraced values, the backward nothing.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): everything
+ * grt_backward refuses (NULL p, no BVH, GRT_OPT_COUNTERS = 1, sh_degree_max > 3, p->t_min <= 0, a window outside the frame, a NULL ray
+ * buffer), meshes set (trace() is the Gaussian-only call), no output (forward: out NULL or all four arrays NULL; backward: out NULL or
+ * all five groups NULL), a NULL d_grad_radiance.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB. */
+typedef struct grt_segments {     /* device pointers, [N] float32 each; NULL = the default for every ray */
+    const float* t_near;          /* NULL: p->t_min */
+    const float* t_far;           /* NULL: p->t_max */
+    const float* T_in;            /* NULL: 1 */
+} grt_segments;
+typedef struct grt_segment_out {  /* device pointers, each may be NULL, not all */
+    float* radiance;              /* [N][3]  R = sum_i T_i alpha_i L_i */
+    float* T_out;                 /* [N]     T_in * prod_i (1 - alpha_i) */
+    float* depth;                 /* [N]     sum_i T_i alpha_i t_i (t_i: the event's key distance, in units of |d|) */
+    uint32_t* count;              /* [N]     composited events */
+} grt_segment_out;
+GRT_API int grt_trace_segments_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_segments* seg,
+                                    const grt_segment_out* out, void* stream);
+GRT_API int grt_trace_segments_frame(grt_ctx* ctx, const grt_params* p, const grt_segments* seg, const grt_segment_out* out, uint32_t x0,
+                                     uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_segments_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_segments* seg,
+                                       const float* d_grad_radiance, const float* d_grad_T_out /* may be NULL */,
+                                       const grt_gaussian_grads* out, void* stream);
+GRT_API int grt_backward_segments_frame(grt_ctx* ctx, const grt_params* p, const grt_segments* seg, const float* d_grad_radiance,
+                                        const float* d_grad_T_out /* may be NULL */, const grt_gaussian_grads* out, uint32_t x0, uint32_t y0,
+                                        uint32_t x1, uint32_t y1, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
