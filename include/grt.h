@@ -808,6 +808,9 @@ GRT_API int grt_backward_events_rays(grt_ctx* ctx, const grt_params* p, const fl
  * FORWARD.  For ray r with a = t_near[r], b = t_far[r], T0 = T_in[r] the events are exactly those trace() composites on [a, b] when it
  * is entered with transmittance T0: key order, entry and exit hits, alpha_min < alpha_i, the 0.99 clamp, T_i = T0 prod_{j<i} (1 -
  * alpha_j), the walk going on while T > minTransmittance (compared with the running T, so T0 counts) and the last distance <= b.
+ * An event whose distance equals t_near or t_far exactly is in NEITHER segment, so a chain cut at an event's own reported distance
+ * (grt_ray_picks, grt_ray_events) loses it: trace() takes a + 1e-9f < t_i < b + 1e-9f in float32, and from 2^-5 on the 1e-9f is
+ * rounded away (below 2^-5 the sum is the next float or the one after, and an event at t_far itself is kept).
  *     radiance [N][3]  R = sum_i T_i alpha_i L_i, accumulated as the frame does: R = R + (L T) alpha
  *     T_out    [N]     T0 prod_i (1 - alpha_i)
  *     depth    [N]     sum_i T_i alpha_i t_i (t_i: the event's key distance, in units of |d|), (T alpha) t added before T is updated

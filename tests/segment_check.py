@@ -15,7 +15,8 @@ term by its absolute value, and T_in for T_out.
 evaluate(): the five gradient groups and their scales.  dL/dalpha_i = g_R . (T_i L_i - S_i / (1 - alpha_i)) - g_T T_out / (1 - alpha_i)
 is formed here; geometry and opacity go through event_check.evaluate_backward, sh through grad_check's basis and sign decisions.
 
-pattern(): the per-ray ranges and T_in every test uses (below).  MEASURED_F32: the float32 evaluation against float64 as error / scale
+pattern(): the per-ray ranges and T_in every test uses (below); block_pattern(): the same kinds assigned per wave, so that whole waves
+are of one kind (keys 'scene/blocks' below); untraced_call(): a call in which no ray is traced.  MEASURED_F32: the float32 evaluation against float64 as error / scale
 per scene, forward and gradients apart, measured on the CPU from the reference walk with fragile rays (margin < grad_check.FRAGILE_REL)
 silenced; every test that holds a walk measures it again and asserts (figure / 2, figure], and the GPU is held to 4 x the scene's own
 figure x scale (DESIGN.md 5.8's margin).  FAULTS: seeded mistakes the comparisons must name (tests/test_segment_check.py).
@@ -44,10 +45,19 @@ MEASURED_F32 = {
     "ragged_rays": {"forward": 3.4e-6, "grad": 9.2e-6},
     "needles": {"forward": 3.3e-6, "grad": 3.2e-3},  # (pos and quat of a needle: event_check.MEASURED_F32 says why)
     "fisheye": {"forward": 2.9e-6, "grad": 9.0e-6},
+    "sh3": {"forward": 2.3e-6, "grad": 2.6e-4},  # (the sh group: 45 higher coefficients per event; the other four at or below 1e-5)
+    # under block_pattern() (whole waves of one kind), ray form and frame form
+    "ragged_rays/blocks": {"forward": 3.1e-6, "grad": 7.8e-6},
+    "inside/blocks": {"forward": 9.1e-7, "grad": 3.8e-6},
+    # 1 M particles with pieces in the tree, pattern() over the 1920x1080 frame, on grad_scenes.sample_mask's rays (pos and quat of a
+    # split particle, as in needles)
+    "C3b_sampled": {"forward": 2.7e-5, "grad": 2.9e-2},
 }
 # fragile rays under pattern() by the walk's own margin, of the traced rays (asserted equal, and under grad_check.MAX_SILENCED)
-MEASURED_FRAGILE = {"cuts": 0, "inside": 10, "ragged_rays": 0, "needles": 11, "fisheye": 4}
-TRACED = {"cuts": 2116, "inside": 5563, "ragged_rays": 2153, "needles": 4556, "fisheye": 5360}
+MEASURED_FRAGILE = {"cuts": 0, "inside": 10, "ragged_rays": 0, "needles": 11, "fisheye": 4, "sh3": 16, "ragged_rays/blocks": 0,
+                    "inside/blocks": 14, "C3b_sampled": 3}
+TRACED = {"cuts": 2116, "inside": 5563, "ragged_rays": 2153, "needles": 4556, "fisheye": 5360, "sh3": 4556, "ragged_rays/blocks": 2005,
+          "inside/blocks": 5148, "C3b_sampled": 4486}
 
 
 def tol_of(name, what):
@@ -95,6 +105,61 @@ def pattern(scene):
     tn[::47] = np.nan
     tf[::53] = np.inf
     return tn, tf, T0
+
+
+UNTRACED_KINDS = ("T_in_0", "T_in_minT", "t_near_nan", "reversed", "t_far_inf")
+
+
+def wave_of(scene, frame_form):
+    """[n] int: the wave a ray runs in — 64 consecutive rays of a buffer, an 8x8 pixel tile of a frame (tiles counted row by row)."""
+    n = len(np.asarray(scene["rays"]).reshape(-1, 6))
+    if not frame_form:
+        return np.arange(n) // 64
+    w, h = scene["p"].width, scene["p"].height
+    assert n == w * h
+    y, x = np.divmod(np.arange(n), w)
+    return (y // 8) * ((w + 7) // 8) + x // 8
+
+
+def block_pattern(scene, frame_form):
+    """(t_near, t_far, T_in) [n] float32: pattern()'s six range kinds and special values assigned per WAVE (wave_of), so that whole
+    waves are of one kind.  By wave mod 4: every ray on the whole range at T_in 1; every ray untraced, one kind per such wave in the
+    order of UNTRACED_KINDS (T_in = 0, T_in = minTransmittance, t_near = NaN, the reversed [s, 0.5 s], t_far = inf); every ray on
+    [s, t_max] at T_in 0.5; pattern()'s own mix."""
+    op = scene["op"]
+    s = closest_param(scene)
+    wv = wave_of(scene, frame_form)
+    tn, tf, T0 = pattern(scene)
+    t_min, t_max = f32(op.t_min), f32(op.t_max)
+    q = wv % 4
+    kind = (wv // 4) % len(UNTRACED_KINDS)
+    whole = (q == 0) | (q == 1)
+    tn[whole] = t_min; tf[whole] = t_max; T0[whole] = f32(1.0)
+    back = q == 2
+    tn[back] = s[back]; tf[back] = t_max; T0[back] = f32(0.5)
+    T0[(q == 1) & (kind == 0)] = 0
+    T0[(q == 1) & (kind == 1)] = f32(op.min_transmittance)
+    tn[(q == 1) & (kind == 2)] = np.nan
+    rev = (q == 1) & (kind == 3)
+    tn[rev] = s[rev]; tf[rev] = (f32(0.5) * s[rev]).astype(f32)
+    tf[(q == 1) & (kind == 4)] = np.inf
+    return tn, tf, T0
+
+
+def untraced_call(scene):
+    """(t_near, t_far, T_in) [n] float32 of a call in which NO ray is traced: the whole range, and every T_in fails T_in >
+    minTransmittance under a bit pattern of its own kind — by r mod 6: +0, -0, a NaN whose payload is r, a negative NaN whose payload is
+    r, -inf and the positive denormal of bits r + 1."""
+    tn, tf, _ = full_range(scene)
+    r = np.arange(len(tn), dtype=np.uint32)
+    assert len(r) < (1 << 22)
+    b = np.zeros(len(r), np.uint32)
+    b[r % 6 == 1] = 0x80000000
+    b[r % 6 == 2] = 0x7FC00000 | r[r % 6 == 2]
+    b[r % 6 == 3] = 0xFFC00000 | r[r % 6 == 3]
+    b[r % 6 == 4] = 0xFF800000
+    b[r % 6 == 5] = r[r % 6 == 5] + 1
+    return tn, tf, b.view(f32)
 
 
 def full_range(scene):

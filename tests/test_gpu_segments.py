@@ -8,7 +8,13 @@ Forward and gradients are held to 4 x the scene's own float32 figure (segment_ch
 hand) x the checker's scale; count and every output of an untraced ray are exact; fragile rays (the walk's own margin below
 grad_check.FRAGILE_REL) are silenced, counted and capped.  Beside the checker: the device against itself, bit for bit (defaults and
 explicit arrays against render_rays_aux, repeats, windows, subsets of outputs, the two-segment chain), against the existing backward,
-the torch layer, the refusals, and a mirror written in torch optimised end to end."""
+the torch layer, the refusals, and a mirror written in torch optimised end to end.
+
+Beside the five scenes: sh3 (SH degree 3, ray form); segment_check.block_pattern on ragged_rays and inside — whole waves of one kind,
+the other side of the kernels' wave-uniform branches — and a call in which no ray is traced; a range end that is bit-equal to an
+event's own distance (the device against itself); state — memory, the next frame, a view, two more streams, the gradient buffer
+shared with backward_rays, a refit and a rebuild from another size; the backward in windows and in groups.  The 1 M frame is
+tests/test_gpu_segments_size.py's."""
 import ctypes as C
 
 import numpy as np
@@ -20,12 +26,15 @@ import grt
 import grt_torch
 import segment_check as SC
 import test_segment_check as TS
+from common import synth
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 DEV = "cuda:0"
-NAMES = ("cuts", "inside", "ragged_rays", "needles", "fisheye")
-FRAME_FORM = ("inside", "fisheye")  # the others hand their camera rays over as a buffer
+NAMES = ("cuts", "inside", "ragged_rays", "needles", "fisheye", "sh3")
+FRAME_FORM = TS.FRAME_FORM  # (inside, fisheye) the others hand their camera rays over as a buffer
+BLOCK_KEYS = ("ragged_rays/blocks", "inside/blocks")  # segment_check.block_pattern: whole waves of one kind, ray form and frame form
+ACT_KEYS = ("pos", "scale", "quat", "opacity", "sh")
 INVALID = -1
 
 
@@ -49,15 +58,20 @@ def tr():
     t.close()
 
 
+def frame_form(name):
+    """name: a scene, or 'scene/blocks' (the scene under the block pattern)"""
+    return name.split("/")[0] in FRAME_FORM
+
+
 def shape_of(s, name):
-    return (s["p"].height, s["p"].width) if name in FRAME_FORM else (len(s["rays"]),)
+    return (s["p"].height, s["p"].width) if frame_form(name) else (len(s["rays"]),)
 
 
 def seg_kw(s, name, tn, tf, T0):
     """The keyword arguments of a trace_segments / backward_segments call of a scene: the frame form, or its rays as a buffer."""
     shp = shape_of(s, name)
     kw = {k: (_t(np.asarray(v, f32)).reshape(shp) if v is not None else None) for k, v in (("t_near", tn), ("t_far", tf), ("T_in", T0))}
-    if name not in FRAME_FORM:
+    if not frame_form(name):
         kw["rays"] = _t(s["rays"])
     return kw
 
@@ -87,6 +101,19 @@ def measured(name):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_forward_against_checker(tr, name):
+    s, w, got = assert_forward_matches(tr, name)
+    n = len(s["rays"])
+    assert (~w.traced).sum() > n // 6
+    if name == "fisheye":
+        assert (~s["live"]).sum() > 100  # pixels without a ray
+    if name == "ragged_rays":
+        assert n % 64 != 0
+    if name == "inside":
+        assert s["p"].width % 8 != 0 and s["p"].height % 8 != 0
+
+
+def assert_forward_matches(tr, name):
+    """name: a scene under the pattern, or 'scene/blocks'.  Returns (scene, Walk, the outputs as numpy)."""
     measured(name)
     s, w, _, _ = case(name)
     n = len(s["rays"])
@@ -102,30 +129,31 @@ def test_forward_against_checker(tr, name):
     frag = SC.fragile(w)
     seen = SC.error_over_scale_forward(got, want, scale, w.traced & ~frag)
     wrong = int((got["count"].reshape(n).astype(np.int64) != want["count"])[~frag | ~w.traced].sum())
-    print(f"{name} ({'frame' if name in FRAME_FORM else 'rays'} form, {n} rays, {int(w.traced.sum())} traced, {len(w.t)} events): {ms:.3f} ms; wrong counts "
+    print(f"{name} ({'frame' if frame_form(name) else 'rays'} form, {n} rays, {int(w.traced.sum())} traced, {len(w.t)} events): {ms:.3f} ms; wrong counts "
           f"{wrong}, error / scale {seen}, bound {SC.tol_of(name, 'forward'):.2e}")
     bad = SC.compare_forward(got, want, scale, SC.tol_of(name, "forward"), frag, w.traced)
     assert not bad, ({k: (len(v), v[:5]) for k, v in bad.items()}, seen)
     # untraced rays: exact zeros and T_in's bits (compare_forward held them to that; once more in the open)
     dead = ~w.traced
-    assert dead.sum() > n // 6
     assert not bits(got["radiance"]).reshape(n, 3)[dead].any() and not bits(got["depth"]).reshape(n)[dead].any()
     assert not got["count"].reshape(n)[dead].any()
     assert np.array_equal(bits(got["T_out"]).reshape(n)[dead], bits(w.T_in)[dead])
-    if name == "fisheye":
-        assert (~s["live"]).sum() > 100  # pixels without a ray
-    if name == "ragged_rays":
-        assert n % 64 != 0
-    if name == "inside":
-        assert s["p"].width % 8 != 0 and s["p"].height % 8 != 0
     # two calls are bitwise equal
     again = _np(tr.trace_segments(s["p"], **seg_kw(s, name, w.t_near, w.t_far, w.T_in)))
     assert all(np.array_equal(bits(again[k]), bits(got[k])) for k in got)
+    return s, w, got
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_gradients_against_checker(tr, name):
     """All five groups, with the wave merge and with plain atomics, the second call accumulating `into` the first's tensors."""
+    got = assert_gradients_match(tr, name)
+    if name == "sh3":  # degree 3 ran: the coefficients of l = 2 and 3 receive gradients
+        assert all(np.abs(got["sh"][:, c]).max() > 0 for c in range(4, 16))
+
+
+def assert_gradients_match(tr, name):
+    """name: a scene under the pattern, or 'scene/blocks'.  Returns the merged call's gradients."""
     measured(name)
     s, w, gR, gT = case(name)
     deg = s["op"].sh_degree_max
@@ -155,6 +183,7 @@ def test_gradients_against_checker(tr, name):
     err2 = G.error_over_scale(got2, twice, {k: 2.0 * scale[k] for k in scale})
     print(f"{name}: plain atomics accumulated into the merged result: error / (2 scale) {err2}")
     assert not G.compare(got2, twice, {k: 2.0 * scale[k] for k in scale}, tol), err2
+    return got
 
 
 def aux_of(tr, p, rays):
@@ -381,6 +410,296 @@ def test_torch_grad_of_T_in_and_a_joint_backward(tr):
     # plain call without gaussians: no graph
     plain = grt_torch.trace_segments(tr, s["p"], rays, _t(w.t_near), _t(w.t_far), _t(w.T_in))
     assert len(plain) == 4 and not plain[0].requires_grad and np.array_equal(bits(plain[0]), bits(R.detach()))
+
+
+# ---- whole waves of one kind (segment_check.block_pattern): the other side of every wave-uniform branch ----
+def run_backward(t, s, name, gR, gT, tn, tf, T0, **kw):
+    shp = shape_of(s, name)
+    g = t.backward_segments(s["p"], _t(gR).reshape(shp + (3,)), _t(gT).reshape(shp) if gT is not None else None, **seg_kw(s, name, tn, tf, T0), **kw)
+    t.sync(); t.check()
+    return g
+
+
+@pytest.mark.parametrize("key", BLOCK_KEYS)
+def test_whole_waves_of_one_kind_against_checker(tr, key):
+    """Waves whose rays are all traced, all untraced (each untraced kind in turn) or all on [s, t_max], beside mixed ones: the
+    forward's sweep skipped by a whole wave, the backward's early return.  ragged_rays: 64 consecutive rays and a partial last wave;
+    inside: 8x8 tiles of a 100x75 frame."""
+    s, w, got = assert_forward_matches(tr, key)
+    n = len(s["rays"])
+    q = SC.wave_of(s, frame_form(key)) % 4
+    assert not w.traced[q == 1].any() and w.traced[q == 0].sum() > 400 and w.traced[q == 2].sum() > 400 and w.traced[q == 3].sum() > 200
+    if frame_form(key):
+        assert s["p"].width % 8 != 0 and s["p"].height % 8 != 0
+    else:
+        assert n % 64 != 0
+    assert_gradients_match(tr, key)
+    # an upstream that is non-zero only on the rays of the untraced waves: every wave returns early, or holds no traced ray with one
+    rng = np.random.default_rng(3)
+    gR, gT = rng.normal(size=(n, 3)).astype(f32), rng.normal(size=n).astype(f32)
+    gR[q != 1] = 0; gT[q != 1] = 0
+    assert (q == 1).sum() > 500
+    for plain in (0, 1):
+        tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, plain)
+        try:
+            g = run_backward(tr, s, key, gR, gT, w.t_near, w.t_far, w.T_in)
+        finally:
+            tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, 0)
+        assert not any(bits(v).any() for v in g.values()), plain
+
+
+@pytest.mark.parametrize("name", ["ragged_rays", "inside"])
+def test_a_call_in_which_no_ray_is_traced(tr, name):
+    """segment_check.untraced_call: every T_in fails T_in > minTransmittance under bits of its own.  Through the C ABI into arrays that
+    hold a sentinel: every element is written — zeros, and T_in's bits; the backward leaves the tensors it accumulates into alone."""
+    s = TS.scene(name)
+    upload(tr, s)
+    p = s["p"]
+    n, shp = len(s["rays"]), shape_of(s, name)
+    tn, tf, T0 = SC.untraced_call(s)
+    assert not SC.is_traced(s["op"], s["rays"], tn, tf, T0, s["live"]).any()
+    out = {k: torch.full(shp + ((3,) if k == "radiance" else ()), -7.0, device=DEV) for k in SC.FLOATS}
+    out["count"] = torch.full(shp, 12345, dtype=torch.int32, device=DEV)
+    keep = [_t(x) for x in (tn, tf, T0)]
+    seg = grt.Segments(*(x.data_ptr() for x in keep))
+    ptrs = grt.SegmentOut(*(out[k].data_ptr() for k in grt.SEGMENT_OUTPUTS))
+    if frame_form(name):
+        rc = grt.lib().grt_trace_segments_frame(tr._h, C.byref(p), C.byref(seg), C.byref(ptrs), 0, 0, p.width, p.height, tr._stream())
+    else:
+        rays = _t(s["rays"])
+        rc = grt.lib().grt_trace_segments_rays(tr._h, C.byref(p), rays.data_ptr(), n, C.byref(seg), C.byref(ptrs), tr._stream())
+    assert rc == 0, grt.lib().grt_last_error(tr._h).decode()
+    tr.sync(); tr.check()
+    assert not bits(out["radiance"]).any() and not bits(out["depth"]).any() and not bits(out["count"]).any()
+    assert np.array_equal(bits(out["T_out"]).reshape(n), bits(T0))
+    # the same through the Python layer, whose tensors are allocated with these values
+    py = _np(tr.trace_segments(p, **seg_kw(s, name, tn, tf, T0)))
+    assert all(np.array_equal(bits(py[k]), bits(out[k])) for k in py)
+    rng = np.random.default_rng(4)
+    gR, gT = rng.normal(size=(n, 3)).astype(f32), rng.normal(size=n).astype(f32)
+    into = {k: _t(rng.normal(size=(len(s["parts"]),) + grt.GRAD_SHAPES[k]).astype(f32)) for k in G.GROUPS}
+    before = {k: bits(v).copy() for k, v in into.items()}
+    for plain in (0, 1):
+        tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, plain)
+        try:
+            assert run_backward(tr, s, name, gR, gT, tn, tf, T0, into=into) is into
+        finally:
+            tr.set_option(grt.OPT_BWD_PLAIN_ATOMICS, 0)
+        assert all(np.array_equal(bits(into[k]), before[k]) for k in into), plain
+
+
+# ---- a range end that is bit-equal to an event's own distance: the device against itself ----
+@pytest.mark.parametrize("name", ["cuts", "ragged_rays"])
+def test_range_end_on_an_events_own_distance(tr, name):
+    """include/grt.h: an event whose distance equals t_near or t_far exactly is in neither segment (gps_round: t_lo <= t < t_hi and
+    key > the start's key, which holds the largest id).  c = t[1] of ray_events, the float32 the device itself reports; [t_min, c] then
+    [c, t_max] with T_out carried in, against the one-segment call, on the rays with at least 3 events that do not end on
+    minTransmittance.  The checker cannot decide this (its t may differ in the last bit); tests/test_segment_check.py asks the oracle.
+    To the letter the two ends are t_far + 1e-9f and t_near + 1e-9f in float32, hi below: c itself from 2^-5 on, where the 1e-9f is
+    rounded away — every ray of cuts and all but a few of ragged_rays (origins inside the cloud: second events at 0.0017 ... 0.03).
+    There hi lies one or two floats behind c, the event at c belongs to the front segment and the chain loses nothing; no ray is
+    left out, the counts are asserted with hi on every ray."""
+    s = TS.scene(name)
+    upload(tr, s)
+    p = s["p"]
+    rays = _t(s["rays"])
+    K = 32
+    ev = tr.ray_events(p, rays=rays, max_events=K)
+    one = tr.trace_segments(p, rays=rays)
+    tr.sync(); tr.check()
+    t, al, cnt = ev["t"].cpu().numpy(), ev["alpha"].cpu().numpy(), ev["count"].cpu().numpy().astype(np.int64)
+    c1 = one["count"].cpu().numpy().astype(np.int64)
+    T1 = one["T_out"].cpu().numpy()
+    assert np.array_equal(cnt, c1)
+    listed = np.arange(K)[:, None] < np.minimum(cnt, K)[None, :]
+    use = (cnt >= 3) & (T1 > f32(p.minTransmittance))  # (T_out is the event list's T behind the last event)
+    c = np.where(use, t[1], f32(1.0)).astype(f32)
+    hi = (c + f32(1e-9)).astype(f32)
+    lt, eq, gt = ((listed & rel(t, hi[None, :])).sum(0) for rel in (np.less, np.equal, np.greater))
+    last_eq = np.where(listed & (t == hi[None, :]), np.arange(K)[:, None], -1).max(0)
+    use &= last_eq < K - 1  # (a tie that runs to the end of the list may go on behind it)
+    at_c = use & (hi == c)
+    assert use.sum() >= 500 and at_c.sum() >= 500, (int(use.sum()), int(at_c.sum()))
+    dc = _t(c)
+    a = tr.trace_segments(p, rays=rays, t_far=dc)
+    b = tr.trace_segments(p, rays=rays, t_near=dc, T_in=a["T_out"])
+    tr.sync(); tr.check()
+    ca, cb = (x["count"].cpu().numpy().astype(np.int64) for x in (a, b))
+    Tb = b["T_out"].cpu().numpy()
+    assert np.array_equal(ca[use], lt[use])
+    full = use & (cnt <= K)  # every event of the ray is listed
+    assert np.array_equal(cb[full], gt[full]) and full.sum() >= 500
+    assert np.array_equal((ca + cb)[use], (c1 - eq)[use]) and (eq[at_c] >= 1).all()  # (where hi is c, the event at c is lost)
+    # the dropped events: only ones the forward does not composite -> the chain's T_out bitwise; else T_out_b (1 - alpha_dropped)
+    dropped = listed & (t == hi[None, :]) & (al > f32(p.alpha_min))
+    keep = np.prod(np.where(dropped, 1.0 - al.astype(np.float64), 1.0), axis=0)
+    none = use & ~dropped.any(0)
+    assert np.array_equal(bits(Tb[none]), bits(T1[none]))
+    some = use & dropped.any(0)
+    err = np.abs(Tb.astype(np.float64) * keep - T1.astype(np.float64))[some]  # (T_out's scale is T_in = 1)
+    print(f"{name}: {int(use.sum())} rays cut at their second event's own distance c ({int((use & ~at_c).sum())} of them with c + 1e-9f > c); "
+          f"{int(eq[use].sum())} events at the cut, in neither segment; "
+          f"{int(none.sum())} rays lose no composited event (T_out bitwise), {int(some.sum())} lose one: max |T_out_b (1 - alpha) - T_out| "
+          f"{err.max() if len(err) else 0.0:.2e}, bound {SC.tol_of(name, 'forward'):.2e}")
+    assert (err <= SC.tol_of(name, "forward")).all()
+
+
+# ---- state: memory, the next frame, views, streams, the shared gradient buffer, updates ----
+def dev(acts):
+    return {k: _t(np.asarray(acts[k], f32)) for k in ACT_KEYS}
+
+
+def frame_bits(t, p):
+    u8, f = t.render(p, want_u8=True, want_f32=True)
+    t.sync(); t.check()
+    return u8.cpu().numpy(), bits(f)
+
+
+def assert_grads_within(got, name, want, scale, what):
+    got = _np(got)
+    err = G.error_over_scale(got, want, scale)
+    print(f"{what}: error / scale {err}, bound {SC.tol_of(name, 'grad'):.2e}")
+    assert not G.compare(got, want, scale, SC.tol_of(name, "grad")), (what, err)
+
+
+def test_no_side_effects_views_and_streams():
+    """cuts under the pattern: slot_bytes and scene_bytes unchanged by a forward and a backward (once a first backward has sized the
+    gradient buffer), the next frame equal to the one before, a view's forward bitwise the tracer's and its backward within the bound,
+    the same on two more streams, and a backward_rays between two backward_segments calls (one gradient buffer) changes nothing."""
+    name = "cuts"
+    measured(name)
+    s, w, gR, gT = case(name)
+    p = s["p"]
+    want, scale = SC.evaluate(s["parts"], w, s["rays"], s["op"].sh_degree_max, gR, gT)
+    rng = (w.t_near, w.t_far, w.T_in)
+    t = grt.Tracer(0)
+    v = None
+    try:
+        upload(t, s)
+        run_backward(t, s, name, gR, gT, *rng)
+        before_frame = frame_bits(t, p)
+        before = t.memory_info()
+        got = _np(t.trace_segments(p, **seg_kw(s, name, *rng)))
+        t.sync(); t.check()
+        assert t.last_kernel_ms() > 0
+        g = run_backward(t, s, name, gR, gT, *rng)
+        after = t.memory_info()
+        print(f"memory before / after a forward and a backward call: {before} / {after}")
+        assert after["slot_bytes"] == before["slot_bytes"] and after["scene_bytes"] == before["scene_bytes"]
+        assert_grads_within(g, name, want, scale, "cuts, tracer")
+        after_frame = frame_bits(t, p)
+        assert np.array_equal(before_frame[0], after_frame[0]) and np.array_equal(before_frame[1], after_frame[1])
+        v = t.view()
+        gv = _np(v.trace_segments(p, **seg_kw(s, name, *rng)))
+        v.sync(); v.check()
+        assert all(np.array_equal(bits(gv[k]), bits(got[k])) for k in got)
+        assert_grads_within(run_backward(v, s, name, gR, gT, *rng), name, want, scale, "cuts, view")
+        assert t.memory_info()["slot_bytes"] == before["slot_bytes"]
+        kw = seg_kw(s, name, *rng)
+        d_gR, d_gT = _t(gR), _t(gT)
+        torch.cuda.synchronize()
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        with torch.cuda.stream(s1):
+            f1 = t.trace_segments(p, **kw)
+            b1 = t.backward_segments(p, d_gR, d_gT, **kw)
+        with torch.cuda.stream(s2):
+            f2 = v.trace_segments(p, **kw)
+            b2 = v.backward_segments(p, d_gR, d_gT, **kw)
+        torch.cuda.synchronize()
+        t.check(); v.check()
+        for f in (f1, f2):
+            assert all(np.array_equal(bits(f[k]), bits(got[k])) for k in got)
+        assert_grads_within(b1, name, want, scale, "cuts, tracer on a second stream")
+        assert_grads_within(b2, name, want, scale, "cuts, view on a third stream")
+        # the slot's gradient buffer is shared with the other backward calls
+        aux = t.render_rays_aux(p, kw["rays"], want_f32=True)
+        first = run_backward(t, s, name, gR, gT, *rng)
+        t.backward_rays(p, kw["rays"], aux["f32"], aux["alpha"], _t(s["gC"]), _t(s["gA"]))
+        second = run_backward(t, s, name, gR, gT, *rng)
+        assert_grads_within(first, name, want, scale, "cuts, before a backward_rays call")
+        assert_grads_within(second, name, want, scale, "cuts, after a backward_rays call")
+    finally:
+        if v is not None:
+            v.close()
+        t.close()
+
+
+def test_after_a_refit_and_after_a_rebuild_of_another_size():
+    """The segments are of the scene the tracer holds NOW: after update_device moved the particles back (refit) and after a rebuild
+    from a scene of another size, forward and gradients match the checker on the scene, with gradient tensors of the new n."""
+    name = "inside"
+    measured(name)
+    s, w, gR, gT = case(name)
+    p, deg = s["p"], s["op"].sh_degree_max
+    acts = s["acts"]
+    rng = np.random.default_rng(23)
+    n = len(acts["pos"])
+    c = acts["pos"].astype(np.float64).mean(0)
+    radius = float(np.sqrt(((acts["pos"] - c) ** 2).sum(1)).max())
+    pert = {k: v.copy() for k, v in acts.items()}
+    pert["pos"] = (pert["pos"] + 0.005 * radius * rng.normal(size=(n, 3))).astype(f32)
+    pert["scale"] = (pert["scale"] * np.exp(0.05 * rng.normal(size=(n, 3)))).astype(f32)
+    want, scale = SC.forward(s["parts"], w, s["rays"], deg)
+    gwant, gscale = SC.evaluate(s["parts"], w, s["rays"], deg, gR, gT)
+    frag = SC.fragile(w)
+    seg = (w.t_near, w.t_far, w.T_in)
+
+    def matches(t, what):
+        got = _np(t.trace_segments(p, **seg_kw(s, name, *seg)))
+        t.sync(); t.check()
+        bad = SC.compare_forward(got, want, scale, SC.tol_of(name, "forward"), frag, w.traced)
+        assert not bad, (what, {k: (len(x), x[:5]) for k, x in bad.items()})
+        g = run_backward(t, s, name, gR, gT, *seg)
+        assert all(tuple(g[k].shape) == (n,) + grt.GRAD_SHAPES[k] for k in G.GROUPS)
+        assert_grads_within(g, name, gwant, gscale, what)
+
+    t = grt.Tracer(0)
+    try:
+        t.upload(pert)
+        moved = _np(t.trace_segments(p, **seg_kw(s, name, *seg)))
+        t.sync(); t.check()
+        assert SC.compare_forward(moved, want, scale, SC.tol_of(name, "forward"), frag, w.traced)  # (the perturbed scene is another scene)
+        info = t.update_device(dev(acts), mode="refit")
+        assert info["mode_used"] == grt.UPDATE_REFIT
+        matches(t, "inside after a refit")
+        _, other = synth(71, 3000, 0.5)
+        t.upload(other)
+        small = run_backward(t, s, name, gR, gT, *seg)
+        assert all(tuple(small[k].shape) == (3000,) + grt.GRAD_SHAPES[k] for k in G.GROUPS)
+        info = t.update_device(dev(acts), mode="auto")
+        assert info["mode_used"] == grt.UPDATE_REBUILD and info["reason"] == grt.REASON_N_CHANGED
+        matches(t, "inside after a rebuild from 3 000 particles")
+    finally:
+        t.close()
+
+
+# ---- the backward in windows and in groups ----
+def test_backward_in_windows_and_in_groups(tr):
+    name = "inside"
+    measured(name)
+    s, w, gR, gT = case(name)
+    p = s["p"]
+    H_, W_ = p.height, p.width
+    want, scale = SC.evaluate(s["parts"], w, s["rays"], s["op"].sh_degree_max, gR, gT)
+    seg = (w.t_near, w.t_far, w.T_in)
+    upload(tr, s)
+    full = _np(run_backward(tr, s, name, gR, gT, *seg))
+    xs, ys = (0, 52, W_), (0, 37, H_)  # no multiple of 8 or 16
+    into = None
+    for j in range(2):
+        for i in range(2):
+            got = run_backward(tr, s, name, gR, gT, *seg, window=(xs[i], ys[j], xs[i + 1], ys[j + 1]), into=into)
+            assert into is None or got is into
+            into = got
+    assert_grads_within(into, name, want, scale, "inside, four windows accumulated")
+    assert_grads_within(into, name, full, scale, "inside, four windows against the full-frame call")
+    for groups in (["pos", "sh"], ["opacity"]):
+        part = run_backward(tr, s, name, gR, gT, *seg, groups=groups)
+        assert sorted(part) == sorted(groups)
+        err = G.error_over_scale(_np(part), {k: want[k] for k in groups}, {k: scale[k] for k in groups})
+        print(f"inside, groups {groups}: error / scale {err}")
+        assert not G.compare(_np(part), {k: want[k] for k in groups}, {k: scale[k] for k in groups}, SC.tol_of(name, "grad")), (groups, err)
+        assert all(np.abs(_np(part)[k]).max() > 0 for k in groups)
 
 
 # ---- refusals ----

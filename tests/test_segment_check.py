@@ -1,9 +1,10 @@
-"""CPU tests of the ray segments' checker (tests/segment_check.py) on the scenes `cuts`, `inside` and `ragged_rays` of
-tests/grad_scenes.py: the walk proves itself ray by ray against Scene.trace under the pattern of ranges and T_in every test uses; in
+"""CPU tests of the ray segments' checker (tests/segment_check.py) on the scenes `cuts`, `inside`, `ragged_rays` and `sh3` (SH degree 3)
+of tests/grad_scenes.py: the walk proves itself ray by ray against Scene.trace under the pattern of ranges and T_in every test uses; in
 float64, at full range and T_in = 1, the gradients are grad_check.evaluate's under gC = g_R / A, gA = -g_T - g_R . R / A; the central
 differences of g_R . R + g_T T_out; the chain identity of two segments on the walk itself; every seeded fault is named; the float32
-figures and the fragile counts are measured again and asserted.  One test holds the built library to the four entry points (it fails
-before they exist)."""
+figures and the fragile counts are measured again and asserted.  The same under segment_check.block_pattern (whole waves of one kind)
+on `ragged_rays`, with the seeded faults named there and on `sh3`; and the oracle's own rule for a range end that is bit-equal to an
+event's distance.  One test holds the built library to the four entry points (it fails before they exist)."""
 import ctypes as C
 import functools
 import os
@@ -15,9 +16,12 @@ import pytest
 import grad_check as G
 import grad_scenes as S
 import grt
+import oracle as O
 import segment_check as SC
 
-NAMES = ("cuts", "inside", "ragged_rays")
+NAMES = ("cuts", "inside", "ragged_rays", "sh3")
+BLOCKS = ("ragged_rays/blocks",)  # segment_check.block_pattern; tests/test_gpu_segments.py holds inside/blocks (frame form) as well
+FRAME_FORM = ("inside", "fisheye")  # the scenes the GPU tests run in the frame form: a wave is an 8x8 tile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
@@ -29,16 +33,17 @@ def scene(name):
 
 @functools.lru_cache(maxsize=None)
 def walked(name, which="pattern"):
-    """(scene, Walk) under SC.pattern (or 'full': SC.full_range); the walk proves every ray it can, or raises CheckerMismatch."""
+    """(scene, Walk) under SC.pattern (or 'full': SC.full_range, 'blocks': SC.block_pattern); the walk proves every ray it can, or
+    raises CheckerMismatch."""
     s = scene(name)
-    tn, tf, T0 = SC.pattern(s) if which == "pattern" else SC.full_range(s)
+    tn, tf, T0 = {"pattern": SC.pattern, "full": SC.full_range, "blocks": lambda s_: SC.block_pattern(s_, name in FRAME_FORM)}[which](s)
     return s, SC.walk(s["parts"], s["op"], s["sc"], s["rays"], tn, tf, T0, s["live"])
 
 
 @functools.lru_cache(maxsize=None)
 def case(name):
-    """(scene, Walk, gR, gT, silenced) under the pattern."""
-    s, w = walked(name)
+    """(scene, Walk, gR, gT, silenced) under the pattern; name 'scene/blocks': under the block pattern."""
+    s, w = walked(name[:-len("/blocks")], "blocks") if name.endswith("/blocks") else walked(name)
     gR, gT, n_sil = SC.upstream(s, w)
     return s, w, gR, gT, n_sil
 
@@ -182,6 +187,91 @@ def test_float32_figures_are_measured_again(name):
     assert_measured(name, SC.measure_f32(s["parts"], w, s["rays"], s["op"].sh_degree_max, gR, gT))
 
 
+@pytest.mark.parametrize("key", BLOCKS)
+def test_block_pattern_walk_proves_and_whole_waves_are_of_one_kind(key):
+    """segment_check.block_pattern: the walk proves itself, the fragile rays are capped and counted, and the waves are what the pattern
+    says — wave mod 4: every ray that can be traced is; none is, under each untraced kind in turn; every ray on [s, t_max]; the mix."""
+    name = key.split("/")[0]
+    s, w = walked(name, "blocks")
+    frag = assert_fragile_capped(key, w, "block pattern")
+    assert int(frag.sum()) == SC.MEASURED_FRAGILE[key] and int(w.traced.sum()) == SC.TRACED[key]
+    assert SC.proved(w).sum() >= 0.99 * w.traced.sum()
+    n = len(w.traced)
+    wv = SC.wave_of(s, name in FRAME_FORM)
+    q = wv % 4
+    can = S.traced(s["rays"], s["live"])  # what a whole-range call traces
+    cnt = SC.counts(w)
+    assert np.array_equal(w.traced[q == 0], can[q == 0]) and (cnt[q == 0] > 0).sum() > 100
+    assert not w.traced[q == 1].any() and not cnt[q == 1].any()
+    assert set(((wv[q == 1] // 4) % len(SC.UNTRACED_KINDS)).tolist()) == set(range(len(SC.UNTRACED_KINDS)))
+    tn, tf, T0 = SC.block_pattern(s, name in FRAME_FORM)
+    one = lambda m, a, v: (a[m].view(np.uint32) == np.asarray(v, f32).view(np.uint32)).all()
+    kind = (wv // 4) % len(SC.UNTRACED_KINDS)
+    assert one((q == 1) & (kind == 0), T0, 0.0) and one((q == 1) & (kind == 1), T0, s["op"].min_transmittance)
+    assert np.isnan(tn[(q == 1) & (kind == 2)]).all() and np.isposinf(tf[(q == 1) & (kind == 4)]).all()
+    with np.errstate(invalid="ignore"):
+        assert not (tn[(q == 1) & (kind == 3)] <= tf[(q == 1) & (kind == 3)]).any()
+    assert one(q == 2, T0, 0.5) and one(q == 2, tf, s["op"].t_max) and np.array_equal(w.traced[q == 2], can[q == 2])
+    assert (cnt[q == 2] > 0).sum() > 100
+    pn, pf, p0 = SC.pattern(s)
+    for a, b in ((tn, pn), (tf, pf), (T0, p0)):
+        assert np.array_equal(a[q == 3].view(np.uint32), b[q == 3].view(np.uint32))
+    if name not in FRAME_FORM:
+        assert n % 64 != 0  # a partial last wave
+    # the call in which no ray is traced: every T_in fails the test under its own bits, nothing is walked, T_out is T_in's bits
+    un, uf, u0 = SC.untraced_call(s)
+    assert not SC.is_traced(s["op"], s["rays"], un, uf, u0, s["live"]).any()
+    assert len(set(u0.view(np.uint32).tolist())) > n // 3
+    w0 = SC.walk(s["parts"], s["op"], s["sc"], s["rays"], un, uf, u0, s["live"])
+    out, _ = SC.forward(s["parts"], w0, s["rays"], s["op"].sh_degree_max, dt=f32)
+    assert len(w0.t) == 0 and np.array_equal(out["T_out"].view(np.uint32), u0.view(np.uint32)) and not out["radiance"].any()
+
+
+@pytest.mark.parametrize("key", BLOCKS)
+def test_block_pattern_figures_are_measured_again(key):
+    s, w, gR, gT, n_sil = case(key)
+    assert n_sil == SC.MEASURED_FRAGILE[key]
+    assert_measured(key, SC.measure_f32(s["parts"], w, s["rays"], s["op"].sh_degree_max, gR, gT))
+
+
+def test_range_end_on_an_events_own_distance_in_the_oracle():
+    """include/grt.h: an event whose distance equals t_near or t_far exactly is in neither segment.  The rule is the oracle's: grto_trace
+    is run on cuts over [t_min, c] and over [c, t_max] with c the oracle's own float32 distance of the ray's second event, and its
+    counter of evaluated hits is compared with the events of the whole-range call in front of c, behind c and at c.  On the rays that
+    do not end on minTransmittance (every hit of every call is evaluated)."""
+    s = scene("cuts")
+    op, sc = s["op"], s["sc"]
+    L = O.lib()
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+
+    def trace(o, d, a, b, T0=f32(1.0)):
+        c = O.Counters()
+        dens = np.array([f32(1.0) - T0], f32); rad = np.zeros(3, f32)
+        L.grto_trace(sc._h, C.byref(op), fp(o), fp(d), float(a), float(b), fp(dens), fp(rad), C.byref(c))
+        return int(c.hit_evals), f32(f32(1.0) - dens[0])
+
+    t_min, t_max, minT = f32(op.t_min), f32(op.t_max), f32(op.min_transmittance)
+    rays = np.asarray(s["rays"], f32).reshape(-1, 6)
+    used = at_c = 0
+    for ri in np.nonzero(S.traced(rays, s["live"]))[0]:
+        o = np.ascontiguousarray(rays[ri, :3]); d = np.ascontiguousarray(rays[ri, 3:])
+        k, _, ts = sc.trace_gps(o, d, float(f32(t_min + G.EPS_T)), float(f32(t_max + G.EPS_T)))
+        n_one, T_one = trace(o, d, t_min, t_max)
+        if k < 3 or not T_one > minT:
+            continue
+        c = ts[1]
+        lt, eq = int((ts[:k] < c).sum()), int((ts[:k] == c).sum())
+        if k == 7 and ts[6] == c:
+            continue  # (the tie may go on into the next round)
+        n_a, T_a = trace(o, d, t_min, c)
+        n_b, T_b = trace(o, d, c, t_max, T_a)
+        assert T_a > minT and T_b > minT
+        assert (n_a, n_b) == (lt, n_one - lt - eq) and eq >= 1, (int(ri), n_a, n_b, n_one, lt, eq)
+        used += 1; at_c += eq
+    print(f"cuts: grto_trace on [t_min, c] and [c, t_max], c the second event's own distance: {used} rays, {at_c} events at c, each in neither segment")
+    assert used >= 500
+
+
 def test_reference_passes_its_own_comparison_at_tolerance_0():
     s, w, gR, gT, _ = case("cuts")
     deg = s["op"].sh_degree_max
@@ -200,7 +290,18 @@ def test_reference_passes_its_own_comparison_at_tolerance_0():
 @pytest.mark.parametrize("fault", SC.FAULTS)
 def test_seeded_faults_are_named(fault):
     """Each mistake a kernel could make, evaluated in float64 on cuts under the pattern, fails the comparison the GPU is held to."""
-    s, w, gR, gT, _ = case("cuts")
+    assert_fault_is_named("cuts", fault)
+
+
+@pytest.mark.parametrize("fault", SC.FAULTS)
+@pytest.mark.parametrize("name", ("sh3",) + BLOCKS)
+def test_seeded_faults_are_named_at_degree_3_and_on_whole_waves(name, fault):
+    """The same on sh3 under the pattern and on ragged_rays under the block pattern, each at the tolerance the GPU is held to there."""
+    assert_fault_is_named(name, fault)
+
+
+def assert_fault_is_named(name, fault):
+    s, w, gR, gT, _ = case(name)
     deg = s["op"].sh_degree_max
     want, scale = SC.forward(s["parts"], w, s["rays"], deg)
     gw, gs = SC.evaluate(s["parts"], w, s["rays"], deg, gR, gT)
@@ -217,9 +318,9 @@ def test_seeded_faults_are_named(fault):
     else:
         got, _ = SC.forward(s["parts"], w, s["rays"], deg, fault=fault if fault == "exit_dropped" else None)
         gg, _ = SC.evaluate(s["parts"], w, s["rays"], deg, gR, gT, fault=fault)
-    bad_f = SC.compare_forward(got, want, scale, SC.tol_of("cuts", "forward"), frag, w.traced)
-    bad_g = G.compare(gg, gw, gs, SC.tol_of("cuts", "grad"))
-    print(f"{fault}: forward names { {k: len(v) for k, v in bad_f.items()} }, gradients name { {k: len(v) for k, v in bad_g.items()} }")
+    bad_f = SC.compare_forward(got, want, scale, SC.tol_of(name, "forward"), frag, w.traced)
+    bad_g = G.compare(gg, gw, gs, SC.tol_of(name, "grad"))
+    print(f"{name}, {fault}: forward names { {k: len(v) for k, v in bad_f.items()} }, gradients name { {k: len(v) for k, v in bad_g.items()} }")
     if fault in ("g_T_wrong_sign", "g_R_times_A"):
         assert not bad_f and {"pos", "scale", "quat", "opacity"} <= set(bad_g)
         if fault == "g_R_times_A":
