@@ -191,7 +191,8 @@ EXPORTS = [
     "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_particle_stats_mesh_frame", "grt_particle_stats_mesh_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
     "grt_ray_events_frame", "grt_ray_events_rays", "grt_backward_events_frame", "grt_backward_events_rays",
     "grt_trace_segments_frame", "grt_trace_segments_rays", "grt_backward_segments_frame", "grt_backward_segments_rays",
-    "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_sync",
+    "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_render_features_mesh_frame", "grt_render_features_mesh_rays",
+    "grt_backward_features_mesh_frame", "grt_backward_features_mesh_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -267,6 +268,10 @@ def lib():
         L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
         L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
         L.grt_backward_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, C.POINTER(FeatureGrads), vp]
+        L.grt_render_features_mesh_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, u32, u32, vp]
+        L.grt_render_features_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, u32, u32, vp]
+        L.grt_backward_features_mesh_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, u32, u32, vp]
+        L.grt_backward_features_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -1046,25 +1051,55 @@ class Tracer:
             shape = (params.height, params.width)
         return feat, rays, shape, (window if window else (0, 0, params.width, params.height)), dev, n
 
+    def _mesh_steps(self, what, steps):
+        """steps = None or (first, last | None) as the (step_first, step_last) of the mesh calls (include/grt.h)."""
+        if steps is None:
+            return 0, 0
+        first, last = steps
+        first, last = int(first), 0 if last is None else int(last)
+        if first < 0 or last < 0 or (steps[1] is not None and last == 0):
+            raise GrtError(f"{what}: steps must be (first, last) with 1 <= first <= last, or last None, not {tuple(steps)}")
+        return first, last
+
     def render_features(self, params, feat, rays=None, window=None):
         """grt_render_features_frame / grt_render_features_rays (rays [n][6] given): the caller's per-particle channels feat
         [n_particles][C] (by original id) composited with the frame's weights, F[ray][c] = sum_i T_i alpha_i feat[id_i][c] over the
         composited events; include/grt.h.  Returns a float32 tensor [h][w][C] (zero outside the window) or [n][C] on the tracer's
         GPU.  F is not multiplied by alpha and not normalised.  Any C >= 1: more than 16 channels run in slices of 16."""
+        return self._render_features("render_features", None, params, feat, rays, window)
+
+    def render_features_mesh(self, params, feat, rays=None, window=None, steps=None):
+        """grt_render_features_mesh_frame / grt_render_features_mesh_rays: render_features() of a frame whose rays bounce off the
+        meshes set on the tracer (include/grt.h) — a particle's channels enter the pixel with the colour weight c_s * T_i * alpha_i its
+        radiance enters the colour with, ONE transmittance running through all of a ray's segments; a mesh surface itself has no
+        feature.  steps = (first, last): only the events of these iterations of the bounce loop carry their feature row (1-based,
+        inclusive; last None = open; None = all): (2, None) is what is seen only through a bounce.  On a tracer without meshes the
+        result is (1 - T_end) * render_features().  Any C >= 1: more than 16 channels run in slices of 16."""
+        return self._render_features("render_features_mesh", self._mesh_steps("render_features_mesh", steps), params, feat, rays, window)
+
+    def _render_features(self, what, steps, params, feat, rays, window):
+        """The checks, the allocation and the calls of render_features (steps None) and render_features_mesh."""
         t = self._torch
-        feat, rays, shape, (x0, y0, x1, y1), dev, n = self._feature_inputs("render_features", params, feat, rays, window)
+        feat, rays, shape, (x0, y0, x1, y1), dev, n = self._feature_inputs(what, params, feat, rays, window)
         C_ = feat.shape[1]
+        L = lib()
         parts = []
         for c0 in range(0, C_, MAX_FEATURE_CHANNELS):
             f = feat[:, c0:c0 + MAX_FEATURE_CHANNELS].contiguous()
             out = t.zeros(shape + (f.shape[1],), dtype=t.float32, device=dev)
             if n and out.numel():
-                if rays is not None:
-                    self._check(lib().grt_render_features_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
-                                                               out.data_ptr(), self._stream()))
+                if rays is not None and steps is None:
+                    self._check(L.grt_render_features_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
+                                                           out.data_ptr(), self._stream()))
+                elif rays is not None:
+                    self._check(L.grt_render_features_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
+                                                                out.data_ptr(), steps[0], steps[1], self._stream()))
+                elif steps is None:
+                    self._check(L.grt_render_features_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], out.data_ptr(), x0, y0, x1, y1,
+                                                            self._stream()))
                 else:
-                    self._check(lib().grt_render_features_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], out.data_ptr(), x0, y0, x1, y1,
-                                                                self._stream()))
+                    self._check(L.grt_render_features_mesh_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], out.data_ptr(), steps[0],
+                                                                 steps[1], x0, y0, x1, y1, self._stream()))
             parts.append(out)
         return parts[0] if len(parts) == 1 else t.cat(parts, -1)
 
@@ -1075,25 +1110,37 @@ class Tracer:
         tensors of `into` (its keys are the groups computed).  'feat' alone is one traversal and uses no buffer of the tracer.  Any
         C >= 1: more than 16 channels run in slices of 16 whose gradients add up (the backward is linear in the upstream).  Not
         bitwise reproducible (float atomics); include/grt.h."""
+        return self._backward_features("backward_features", None, params, feat, grad_out, rays, window, into, groups)
+
+    def backward_features_mesh(self, params, feat, grad_out, rays=None, window=None, into=None, groups=None, steps=None):
+        """grt_backward_features_mesh_frame / grt_backward_features_mesh_rays: backward_features() for the F of render_features_mesh
+        (same params, feat, rays / window, steps) on a frame whose rays bounce off the tracer's meshes; the meshes and every discrete
+        decision are held fixed (include/grt.h).  A ray is walked twice, also for 'feat' alone (which uses no buffer of the tracer)."""
+        return self._backward_features("backward_features_mesh", self._mesh_steps("backward_features_mesh", steps), params, feat, grad_out,
+                                       rays, window, into, groups)
+
+    def _backward_features(self, what, steps, params, feat, grad_out, rays, window, into, groups):
+        """The checks, the allocation and the calls of backward_features (steps None) and backward_features_mesh."""
         t = self._torch
-        feat, rays, shape, (x0, y0, x1, y1), dev, n = self._feature_inputs("backward_features", params, feat, rays, window)
+        feat, rays, shape, (x0, y0, x1, y1), dev, n = self._feature_inputs(what, params, feat, rays, window)
         C_ = feat.shape[1]
         grad_out = t.as_tensor(grad_out).detach().to(dev, t.float32).contiguous()
         if tuple(grad_out.shape) != shape + (C_,):
-            raise GrtError(f"backward_features: grad_out must have shape {shape + (C_,)}, not {tuple(grad_out.shape)}")
+            raise GrtError(f"{what}: grad_out must have shape {shape + (C_,)}, not {tuple(grad_out.shape)}")
         shapes = {k: ((C_,) if k == "feat" else GRAD_SHAPES[k]) for k in FEATURE_GROUPS}
         if into is None:
             bad = [k for k in (groups if groups is not None else ()) if k not in FEATURE_GROUPS]
             if bad or (groups is not None and not len(groups)):
-                raise GrtError(f"backward_features: groups must be a non-empty subset of {FEATURE_GROUPS}, not {tuple(groups)}")
+                raise GrtError(f"{what}: groups must be a non-empty subset of {FEATURE_GROUPS}, not {tuple(groups)}")
             into = {k: t.zeros((n,) + shapes[k], dtype=t.float32, device=dev) for k in (groups if groups is not None else FEATURE_GROUPS)}
         for k, v in into.items():
             if k not in FEATURE_GROUPS or tuple(v.shape) != (n,) + shapes[k] or v.dtype != t.float32 or not v.is_contiguous() or v.device != dev:
-                raise GrtError(f"backward_features: gradient tensor '{k}' must be contiguous float32 of shape {(n,) + shapes[k]} on {dev}")
+                raise GrtError(f"{what}: gradient tensor '{k}' must be contiguous float32 of shape {(n,) + shapes[k]} on {dev}")
         if not into:
-            raise GrtError("backward_features: no gradient group asked for")
+            raise GrtError(f"{what}: no gradient group asked for")
         if not n or not grad_out.numel():
             return into
+        L = lib()
         sliced = C_ > MAX_FEATURE_CHANNELS
         for c0 in range(0, C_, MAX_FEATURE_CHANNELS):
             f = feat[:, c0:c0 + MAX_FEATURE_CHANNELS].contiguous()
@@ -1102,12 +1149,18 @@ class Tracer:
             if "feat" in into:  # (a slice of the [n][C] tensor is not contiguous: its gradient goes through a tensor of its own)
                 gf = t.zeros_like(f) if sliced else into["feat"]
             ptrs = FeatureGrads(*(into[k].data_ptr() if k in into else None for k in FEATURE_GROUPS[:4]), gf.data_ptr() if gf is not None else None)
-            if rays is not None:
-                self._check(lib().grt_backward_features_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
-                                                             g.data_ptr(), C.byref(ptrs), self._stream()))
+            if rays is not None and steps is None:
+                self._check(L.grt_backward_features_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
+                                                         g.data_ptr(), C.byref(ptrs), self._stream()))
+            elif rays is not None:
+                self._check(L.grt_backward_features_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], f.data_ptr(), f.shape[1],
+                                                              g.data_ptr(), C.byref(ptrs), steps[0], steps[1], self._stream()))
+            elif steps is None:
+                self._check(L.grt_backward_features_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], g.data_ptr(), C.byref(ptrs),
+                                                          x0, y0, x1, y1, self._stream()))
             else:
-                self._check(lib().grt_backward_features_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], g.data_ptr(), C.byref(ptrs),
-                                                              x0, y0, x1, y1, self._stream()))
+                self._check(L.grt_backward_features_mesh_frame(self._h, C.byref(params), f.data_ptr(), f.shape[1], g.data_ptr(), C.byref(ptrs),
+                                                               steps[0], steps[1], x0, y0, x1, y1, self._stream()))
             if gf is not None and sliced:
                 into["feat"][:, c0:c0 + MAX_FEATURE_CHANNELS] += gf
         return into

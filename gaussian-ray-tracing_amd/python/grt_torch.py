@@ -254,14 +254,18 @@ def ray_events(tracer, params, geometry=None, rays=None, window=None, max_events
 
 class _RenderFeatures(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, pos, scale, quat, opacity, rays, tracer, params):
+    def forward(ctx, feat, pos, scale, quat, opacity, rays, tracer, params, mesh, steps):
         # pos .. opacity: the tensors of the tracer's last upload (or None): only the carriers of the geometry gradients
+        # mesh: the calls that follow the rays through the tracer's meshes (Tracer.render_features_mesh), with their step range
         ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
         ctx.upload_id = ctx.scene.n_uploads
         ctx.tracer, ctx.params = tracer, params
+        ctx.mesh, ctx.steps = mesh, steps
         ctx.rays = rays.detach() if rays is not None else None
         ctx.like = tuple((t.device, t.dtype) if t is not None else None for t in (feat, pos, scale, quat, opacity))
         ctx.save_for_backward(feat.detach())
+        if mesh:
+            return tracer.render_features_mesh(params, feat.detach(), rays=ctx.rays, steps=steps)
         return tracer.render_features(params, feat.detach(), rays=ctx.rays)
 
     @staticmethod
@@ -274,12 +278,15 @@ class _RenderFeatures(torch.autograd.Function):
         names = ("feat", "pos", "scale", "quat", "opacity")
         groups = [n for n, want in zip(names, ctx.needs_input_grad[:5]) if want]
         if not groups:
-            return (None,) * 8
-        g = tr.backward_features(ctx.params, feat, g_out, rays=ctx.rays, groups=groups)
-        return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 3
+            return (None,) * 10
+        if ctx.mesh:
+            g = tr.backward_features_mesh(ctx.params, feat, g_out, rays=ctx.rays, groups=groups, steps=ctx.steps)
+        else:
+            g = tr.backward_features(ctx.params, feat, g_out, rays=ctx.rays, groups=groups)
+        return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 5
 
 
-def render_features(tracer, params, feat, rays=None, geometry=None):
+def render_features(tracer, params, feat, rays=None, geometry=None, through_meshes=False, steps=None):
     """F [h][w][C] (or [n][C] for `rays` [n][6]) of the per-particle channels feat [n_particles][C] composited with the frame's
     weights T_i alpha_i (Tracer.render_features; include/grt.h: grt_render_features_frame / _rays), differentiable with respect to
     feat and, with geometry=(pos, scale, quat, opacity), with respect to those four as well.  Any C >= 1.
@@ -287,10 +294,17 @@ def render_features(tracer, params, feat, rays=None, geometry=None):
     grt_torch.render_features(tracer, ...) can share one loss.backward().  The `geometry` tensors only carry the gradient — they
     must be the tensors of the tracer's last upload (the ones given to grt_torch.render), their shapes are checked against the
     tracer's particle count and their values are not read.  The backward raises GrtError when the tracer has received another upload
-    since the forward.  Gradients with respect to rays are not computed (`rays` that requires grad: ValueError), and neither are
-    mesh frames (a tracer with meshes: ValueError)."""
-    if tracer.has_meshes:
-        raise ValueError("grt_torch.render_features: meshes are set on this tracer; feature channels are rendered for Gaussian-only frames")
+    since the forward.  Gradients with respect to rays are not computed (`rays` that requires grad: ValueError).
+    through_meshes=True, or steps=(first, last) given, sends the call to Tracer.render_features_mesh / backward_features_mesh
+    (include/grt.h: grt_render_features_mesh_*), on a tracer with or without meshes: the rays bounce as the frame's do, and a particle's
+    channels enter the pixel with the colour weight c_s T_i alpha_i its radiance enters the colour with — what a mirror or glass shows
+    carries its features, the surface itself has none.  steps: only the events of these iterations of the bounce loop carry their
+    feature row (1-based, inclusive, last None = open): (2, None) is what is seen only through a bounce.  The meshes are held fixed.
+    With the default through_meshes=False a tracer with meshes raises ValueError (the plain F is defined for Gaussian-only frames)."""
+    mesh = bool(through_meshes) or steps is not None
+    if tracer.has_meshes and not mesh:
+        raise ValueError("grt_torch.render_features: meshes are set on this tracer; feature channels are rendered for Gaussian-only frames "
+                         "(pass through_meshes=True to render them through the bounces)")
     if rays is not None and rays.requires_grad:
         raise ValueError("grt_torch.render_features: gradients with respect to rays are not computed through features; detach rays")
     geo = (None,) * 4
@@ -305,7 +319,7 @@ def render_features(tracer, params, feat, rays=None, geometry=None):
             if tuple(t.shape) != shape:
                 raise ValueError(f"grt_torch.render_features: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
                                  f"not {tuple(t.shape)}")
-    return _RenderFeatures.apply(feat, *geo, rays, tracer, params)
+    return _RenderFeatures.apply(feat, *geo, rays, tracer, params, mesh, steps)
 
 
 class _TraceSegments(torch.autograd.Function):

@@ -629,7 +629,8 @@ GRT_API int grt_particle_stats_rays(grt_ctx* ctx, const grt_params* p, const flo
  * On a scene WITHOUT meshes a ray has one last pass: count, weight_max and weight_sum are the plain call's, cw_i = (1 - T_end) w_i.
  * Refused with GRT_ERR_INVALID like the plain call, without its meshes row: GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a
  * window outside the frame, sh_degree_max > 3, t_min <= 0; and p->type outside MIRROR/NORMAL/GLASS, step_first > step_last with
- * step_last != 0.  GRT_ERR_LIMIT as in the backward.  Not computed on mesh frames: picks, event lists, feature channels. */
+ * step_last != 0.  GRT_ERR_LIMIT as in the backward.  Not computed on mesh frames: picks, event lists (feature channels:
+ * grt_render_features_mesh_frame, below). */
 typedef struct {
     float* weight_sum;
     float* weight_max;
@@ -680,7 +681,7 @@ GRT_API int grt_particle_stats_mesh_rays(grt_ctx* ctx, const grt_params* p, cons
  * buffer), meshes set (feature channels are rendered for Gaussian-only frames), channels 0 or above GRT_MAX_FEATURE_CHANNELS, a NULL
  * feat, output or upstream.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB, as in the backward.
  * Not computed: gradients with respect to rays or the camera through features, an alpha / depth / normalised output (grt_render_aux
- * has alpha), mesh frames. */
+ * has alpha); mesh frames have calls of their own (grt_render_features_mesh_frame, below). */
 #define GRT_MAX_FEATURE_CHANNELS 16
 typedef struct {
     float* pos;
@@ -697,6 +698,51 @@ GRT_API int grt_backward_features_frame(grt_ctx* ctx, const grt_params* p, const
                                         const grt_feature_grads* grads, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_backward_features_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_feat,
                                        uint32_t channels, const float* d_grad_out, const grt_feature_grads* grads, void* stream);
+/* ---- feature channels of MESH frames: what a view shows through mirrors and glass, with gradients ----
+ * The feature calls above for a scene with meshes set (grt_set_meshes): rays bounce as grt_render / grt_render_aux trace them, and
+ * the particles met behind a bounce enter the pixel's features with the weight their radiance enters its colour with.  A ray runs
+ * iterations s = 1..S exactly as documented at grt_backward_mesh: ONE event list with ONE running transmittance carried through
+ * `density`, the same composited events.  feat[n][C], channels (1 .. GRT_MAX_FEATURE_CHANNELS), the output layout and the untraced
+ * rays (zeros) are the plain calls'.
+ * FORWARD.  Per segment, in compositing order and in float32 without contraction (Phi = Phi + w_i * f_c, as the plain call forms F),
+ *     Phi_s[c] = sum_{i in s} w_i feat[id_i][c],     w_i = T_i alpha_i,
+ * and at the iteration's step of the loop F[c] = F[c] + Phi_s[c] * c_s with the segment's colour weight of
+ * grt_particle_stats_mesh, formed in float32 as the forward forms it:
+ *     c_s = 1 - A_{s-1}   Gaussian pass;     D_S (1 - B_{S-1})   last pass;     1   a terminating GRT_NORMAL hit.
+ * A mesh surface itself contributes NO feature (the ncol (1 - D_s) term of the colour has no counterpart), and nothing is clamped.
+ * On a scene WITHOUT meshes a ray has one last pass, so F = (1 - T_end) F_plain: the mesh calls weight with the frame's own alpha,
+ * the plain calls do not.  With feat[j] = particle j's radiance F is the frame's rgbf on every frame that neither clamps a radiance
+ * channel nor ends on a GRT_NORMAL hit.  Plain stores, no atomic: bitwise reproducible, and windows tile a frame bit for bit.
+ *   step_first, step_last   as for grt_particle_stats_mesh: the iterations whose events carry their feature row, 1-based, inclusive;
+ *                  0, 0 = all; step_last = 0 leaves the range open.  Events outside the range are still composited — T, A and B run
+ *                  through them — with a feature row of ZERO.  (2, 0) renders what is seen only through a bounce.
+ * BACKWARD of loss = sum_ray sum_c g[ray][c] F[ray][c], every discrete decision of grt_backward_mesh held fixed.  Per event
+ * phi_i = sum_c g_c feat[id_i][c], and 0 for an event outside the step range; dloss/dalpha_i is grt_backward_mesh's formula with the
+ * one-channel radiance L_i = (phi_i, 0, 0), g_C = (1, 0, 0), g_A = 0, no ncol term and no radiance clamp; below alpha_i the chain to
+ * pos, scale, quat and opacity is unchanged (with the segment's own ray); and
+ *     dloss/dfeat[j][c] += sum over the composited events i of particle j inside the step range of  c_s w_i g[ray][c].
+ * All gradients are ADDED into the caller's arrays; any subset of the five may be NULL, all five NULL: GRT_ERR_INVALID.  A ray whose C
+ * upstream values are all exactly 0 is not traced.  A ray is walked twice (D_S is known only at the end of the last segment), also
+ * for the feature gradient alone; that call touches no buffer of the context, the others go through its gradient buffer and flush
+ * as grt_backward_mesh.  Float atomics (GRT_OPT_BWD_PLAIN_ATOMICS applies).  The forward uses no buffer of the context; a frame rendered
+ * after either call is bit-identical to one rendered before it; a view computes its scene's result.  With no rays, no particles or
+ * an empty tree the calls return GRT_OK: the forward writes zeros, the backward nothing.
+ * Refused with GRT_ERR_INVALID (the entry point's name in front; the context stays usable) like the plain calls, without their
+ * meshes row: NULL p, no BVH, GRT_OPT_COUNTERS = 1, sh_degree_max > 3, t_min <= 0, a window outside the frame, a NULL ray buffer,
+ * channels 0 or above GRT_MAX_FEATURE_CHANNELS, a NULL feat, output or upstream; and p->type outside MIRROR/NORMAL/GLASS,
+ * step_first > step_last with step_last != 0.  GRT_ERR_LIMIT as in the mesh backward (the LDS stack of the higher of the two trees).
+ * Not computed: picks and event lists on mesh frames, gradients with respect to rays, camera or meshes, a feature of the surface. */
+GRT_API int grt_render_features_mesh_frame(grt_ctx* ctx, const grt_params* p, const float* d_feat, uint32_t channels, float* d_out,
+                                           uint32_t step_first, uint32_t step_last, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                                           void* stream);
+GRT_API int grt_render_features_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_feat,
+                                          uint32_t channels, float* d_out, uint32_t step_first, uint32_t step_last, void* stream);
+GRT_API int grt_backward_features_mesh_frame(grt_ctx* ctx, const grt_params* p, const float* d_feat, uint32_t channels,
+                                             const float* d_grad_out, const grt_feature_grads* grads, uint32_t step_first,
+                                             uint32_t step_last, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_features_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_feat,
+                                            uint32_t channels, const float* d_grad_out, const grt_feature_grads* grads,
+                                            uint32_t step_first, uint32_t step_last, void* stream);
 /* ---- per-ray picks: which particle a ray sees first, strongest and at its median, and where (Gaussian-only frames) ----
  * What picking and lasso selection in a viewer, per-pixel id and label maps, and a surface depth (TSDF fusion, mesh extraction, depth
  * regularisers) read: grt_aux_out::depth is the expected distance sum w_i t_i and smears across silhouettes; the particle statistics
