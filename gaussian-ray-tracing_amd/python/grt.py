@@ -118,6 +118,27 @@ class RayEvents(C.Structure):
                 ("first", C.c_uint32), ("max_events", C.c_uint32)]
 
 
+class PickMeshOut(C.Structure):
+    """grt_pick_mesh_out (include/grt.h): device pointers of one rule's id / t / weight / step / point arrays, each may be NULL."""
+    _fields_ = [("id", C.c_void_p), ("t", C.c_void_p), ("weight", C.c_void_p), ("step", C.c_void_p), ("point", C.c_void_p)]
+
+
+class RayPicksMesh(C.Structure):
+    """grt_ray_picks_mesh (include/grt.h): the three rules' outputs, the transmittance the cross rule waits for and the iterations
+    whose events are candidates (1-based, inclusive; 0, 0 = all)."""
+    _fields_ = [("first", PickMeshOut), ("peak", PickMeshOut), ("cross", PickMeshOut), ("cross_T", C.c_float),
+                ("step_first", C.c_uint32), ("step_last", C.c_uint32)]
+
+
+class RayEventsMesh(C.Structure):
+    """grt_ray_events_mesh (include/grt.h): device pointers of the slot-major id / t / alpha / step arrays [K][N], of count / T_in [N],
+    of the path arrays [P][N] and of n_steps [N], each may be NULL; the first listed event, K = max_events, the step range, P = max_steps."""
+    _fields_ = [("id", C.c_void_p), ("t", C.c_void_p), ("alpha", C.c_void_p), ("step", C.c_void_p), ("count", C.c_void_p), ("T_in", C.c_void_p),
+                ("first", C.c_uint32), ("max_events", C.c_uint32), ("step_first", C.c_uint32), ("step_last", C.c_uint32),
+                ("path_rays", C.c_void_p), ("path_t_far", C.c_void_p), ("path_state", C.c_void_p), ("n_steps", C.c_void_p),
+                ("max_steps", C.c_uint32)]
+
+
 class Segments(C.Structure):
     """grt_segments (include/grt.h): device pointers of the per-ray t_near / t_far / T_in arrays [N], each may be NULL (p->t_min,
     p->t_max, 1 for every ray)."""
@@ -153,6 +174,10 @@ PICK_FIELDS = ("id", "t", "weight")
 FEATURE_GROUPS = ("pos", "scale", "quat", "opacity", "feat")
 EVENT_FIELDS = ("id", "t", "alpha", "count", "T_in")
 EVENT_GROUPS = ("pos", "scale", "quat", "opacity")
+MESH_PICK_FIELDS = PICK_FIELDS + ("step", "point")
+MESH_EVENT_FIELDS = ("id", "t", "alpha", "step", "count", "T_in")
+MESH_PATH_FIELDS = ("path_rays", "path_t_far", "path_state", "n_steps")
+STEP_LAST, STEP_GAUSSIAN, STEP_TERMINATE = 0, 1, 3  # GRT_STEP_*: the states in path_state (PICK_NONE: an unused path slot)
 SEGMENT_OUTPUTS = ("radiance", "T_out", "depth", "count")
 
 
@@ -190,6 +215,8 @@ EXPORTS = [
     "grt_render_rays_aux", "grt_backward", "grt_backward_rays", "grt_backward_ex", "grt_backward_rays_ex", "grt_backward_mesh", "grt_backward_rays_mesh",
     "grt_particle_stats_frame", "grt_particle_stats_rays", "grt_particle_stats_mesh_frame", "grt_particle_stats_mesh_rays", "grt_ray_picks_frame", "grt_ray_picks_rays",
     "grt_ray_events_frame", "grt_ray_events_rays", "grt_backward_events_frame", "grt_backward_events_rays",
+    "grt_ray_picks_mesh_frame", "grt_ray_picks_mesh_rays", "grt_ray_events_mesh_frame", "grt_ray_events_mesh_rays",
+    "grt_backward_events_mesh_frame", "grt_backward_events_mesh_rays",
     "grt_trace_segments_frame", "grt_trace_segments_rays", "grt_backward_segments_frame", "grt_backward_segments_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_render_features_mesh_frame", "grt_render_features_mesh_rays",
     "grt_backward_features_mesh_frame", "grt_backward_features_mesh_rays", "grt_sync",
@@ -260,6 +287,12 @@ def lib():
         L.grt_ray_events_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayEvents), vp]
         L.grt_backward_events_frame.argtypes = [vp, C.POINTER(Params), vp, u32, u32, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
         L.grt_backward_events_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, u32, C.POINTER(GaussianGrads), vp]
+        L.grt_ray_picks_mesh_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayPicksMesh), u32, u32, u32, u32, vp]
+        L.grt_ray_picks_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayPicksMesh), vp]
+        L.grt_ray_events_mesh_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(RayEventsMesh), u32, u32, u32, u32, vp]
+        L.grt_ray_events_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(RayEventsMesh), vp]
+        L.grt_backward_events_mesh_frame.argtypes = [vp, C.POINTER(Params), vp, u32, u32, u32, u32, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
+        L.grt_backward_events_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, u32, u32, u32, C.POINTER(GaussianGrads), vp]
         L.grt_trace_segments_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(Segments), C.POINTER(SegmentOut), u32, u32, u32, u32, vp]
         L.grt_trace_segments_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(Segments), C.POINTER(SegmentOut), vp]
         L.grt_backward_segments_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(Segments), vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
@@ -941,6 +974,118 @@ class Tracer:
         else:
             self._check(lib().grt_backward_events_frame(self._h, C.byref(params), grad_alpha.data_ptr(), first, K, C.byref(ptrs),
                                                         x0, y0, x1, y1, self._stream()))
+        return into
+
+    def ray_picks_mesh(self, params, rays=None, window=None, cross_T=0.5, picks=PICK_RULES, fields=MESH_PICK_FIELDS, steps=None):
+        """grt_ray_picks_mesh_frame / grt_ray_picks_mesh_rays: ray_picks() of a frame whose rays bounce off the meshes set
+        (mirror, glass, normal) -> {pick: {field: tensor}}; include/grt.h.  Beside 'id', 't' and 'weight' every pick has 'step' (uint32,
+        the 1-based iteration of the bounce loop the event was met in; 0 where none) and 'point' (float32 [..][3], the world position
+        o_s + t d_s on that iteration's ray); 't' is measured along that ray.  steps = (first, last): only the events of these
+        iterations are candidates (1-based, inclusive; last None: open; None: all) — (2, None) picks what is seen only through a bounce;
+        the cross rule tests the ray's own transmittance whatever the range.  Bitwise reproducible; nothing here is differentiable."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        picks, fields = tuple(picks), tuple(fields)
+        if not picks or any(k not in PICK_RULES for k in picks):
+            raise GrtError(f"ray_picks_mesh: picks must be a non-empty subset of {PICK_RULES}, not {picks}")
+        if not fields or any(k not in MESH_PICK_FIELDS for k in fields):
+            raise GrtError(f"ray_picks_mesh: fields must be a non-empty subset of {MESH_PICK_FIELDS}, not {fields}")
+        if "cross" in picks and not 0.0 < float(cross_T) < 1.0:
+            raise GrtError(f"ray_picks_mesh: cross_T must lie in (0, 1), not {cross_T}")
+        s_first, s_last = self._mesh_steps("ray_picks_mesh", steps)
+        if rays is not None:
+            if window is not None:
+                raise GrtError("ray_picks_mesh: rays and window exclude each other")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"ray_picks_mesh: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        # (PICK_NONE is int32 -1: filled as such, the kernels of the wider unsigned types are not everywhere)
+        make = {"id": lambda: t.full(shape, -1, dtype=t.int32, device=dev).view(t.uint32),
+                "t": lambda: t.zeros(shape, dtype=t.float32, device=dev),
+                "weight": lambda: t.zeros(shape, dtype=t.float32, device=dev),
+                "step": lambda: t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32),
+                "point": lambda: t.zeros(shape + (3,), dtype=t.float32, device=dev)}
+        out = {k: {f: make[f]() for f in MESH_PICK_FIELDS if f in fields} for k in PICK_RULES if k in picks}
+        if not n or not shape[0] or not shape[-1]:  # (an empty scene or no ray: every element is "none" already)
+            return out
+        ptrs = RayPicksMesh(*(PickMeshOut(*(out[k][f].data_ptr() if k in out and f in out[k] else None for f in MESH_PICK_FIELDS))
+                              for k in PICK_RULES), float(cross_T), s_first, s_last)
+        if rays is not None:
+            self._check(lib().grt_ray_picks_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], C.byref(ptrs), self._stream()))
+        else:
+            x0, y0, x1, y1 = window if window else (0, 0, params.width, params.height)
+            self._check(lib().grt_ray_picks_mesh_frame(self._h, C.byref(params), C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return out
+
+    def ray_events_mesh(self, params, rays=None, window=None, max_events=32, first=0, fields=MESH_EVENT_FIELDS, steps=None, max_steps=0):
+        """grt_ray_events_mesh_frame / grt_ray_events_mesh_rays: ray_events() of a frame whose rays bounce off the meshes set -> dict of
+        torch tensors; include/grt.h.  The events of the iterations `steps` (as ray_picks_mesh; None: all) are numbered over the whole
+        ray; beside 'id', 't', 'alpha' [K][..] there is 'step' (uint32 [K][..], the event's 1-based iteration; 0 unused), 't' measured on
+        that iteration's ray.  max_steps = P > 0 adds the ray's path: 'path_rays' [P][..][6] (o_s, d_s of iteration slot + 1),
+        'path_t_far' [P][..], 'path_state' (uint32 [P][..]: STEP_LAST, STEP_GAUSSIAN, STEP_TERMINATE; PICK_NONE unused) and 'n_steps'
+        (uint32 [..], ALL iterations, not capped by P).  Bitwise reproducible; backward_events_mesh takes dloss/dalpha back."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, K, first = self._event_inputs("ray_events_mesh", params, rays, window, max_events, first)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        fields, P = tuple(fields), int(max_steps)
+        if not fields or any(k not in MESH_EVENT_FIELDS for k in fields):
+            raise GrtError(f"ray_events_mesh: fields must be a non-empty subset of {MESH_EVENT_FIELDS}, not {fields}")
+        if P < 0 or P > 0xFFFFFFFF:
+            raise GrtError(f"ray_events_mesh: max_steps must be >= 0, not {max_steps}")
+        s_first, s_last = self._mesh_steps("ray_events_mesh", steps)
+        # (PICK_NONE is int32 -1: filled as such, the kernels of the wider unsigned types are not everywhere)
+        make = {"id": lambda: t.full((K,) + shape, -1, dtype=t.int32, device=dev).view(t.uint32),
+                "t": lambda: t.zeros((K,) + shape, dtype=t.float32, device=dev),
+                "alpha": lambda: t.zeros((K,) + shape, dtype=t.float32, device=dev),
+                "step": lambda: t.zeros((K,) + shape, dtype=t.int32, device=dev).view(t.uint32),
+                "count": lambda: t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32),
+                "T_in": lambda: t.ones(shape, dtype=t.float32, device=dev)}
+        out = {k: make[k]() for k in MESH_EVENT_FIELDS if k in fields}
+        if P:
+            out["path_rays"] = t.zeros((P,) + shape + (6,), dtype=t.float32, device=dev)
+            out["path_t_far"] = t.zeros((P,) + shape, dtype=t.float32, device=dev)
+            out["path_state"] = t.full((P,) + shape, -1, dtype=t.int32, device=dev).view(t.uint32)
+            out["n_steps"] = t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32)
+        if not n or not shape[0] or not shape[-1]:  # (an empty scene or no ray: every element is "no event" already)
+            return out
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        ptrs = RayEventsMesh(*(ptr(k) for k in MESH_EVENT_FIELDS), first, K, s_first, s_last, *(ptr(k) for k in MESH_PATH_FIELDS), P)
+        if rays is not None:
+            self._check(lib().grt_ray_events_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], C.byref(ptrs), self._stream()))
+        else:
+            self._check(lib().grt_ray_events_mesh_frame(self._h, C.byref(params), C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return out
+
+    def backward_events_mesh(self, params, grad_alpha, rays=None, window=None, first=0, into=None, groups=None, steps=None):
+        """grt_backward_events_mesh_frame / grt_backward_events_mesh_rays: backward_events() for the lists of ray_events_mesh (same
+        params, rays / window, first and steps; K is grad_alpha's first dimension).  Every listed alpha is differentiated on its own
+        iteration's ray, the mesh hits and the next rays held fixed.  One traversal; float atomics; include/grt.h."""
+        t = self._torch
+        if not t.is_tensor(grad_alpha) or grad_alpha.dim() < 2:
+            raise GrtError("backward_events_mesh: grad_alpha must be a tensor of shape [K][h][w] or [K][n]")
+        rays, shape, (x0, y0, x1, y1), dev, K, first = self._event_inputs("backward_events_mesh", params, rays, window, grad_alpha.shape[0], first)
+        if tuple(grad_alpha.shape) != (K,) + shape:
+            raise GrtError(f"backward_events_mesh: grad_alpha must have shape [K]{list(shape)}, not {tuple(grad_alpha.shape)}")
+        grad_alpha = grad_alpha.detach().to(dev, t.float32).contiguous()
+        if "sh" in (into if into is not None else (groups if groups is not None else ())):
+            raise GrtError("backward_events_mesh: 'sh' is not a group of this call (colour does not depend on the listed events' alpha)")
+        if (into is not None and not into) or (into is None and groups is not None and not len(groups)):
+            raise GrtError("backward_events_mesh: no gradient group asked for")
+        s_first, s_last = self._mesh_steps("backward_events_mesh", steps)
+        into, ptrs = self._grad_buffers(into, groups if groups is not None else EVENT_GROUPS, dev)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if not n or not grad_alpha.numel():
+            return into
+        if rays is not None:
+            self._check(lib().grt_backward_events_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], grad_alpha.data_ptr(), first, K,
+                                                            s_first, s_last, C.byref(ptrs), self._stream()))
+        else:
+            self._check(lib().grt_backward_events_mesh_frame(self._h, C.byref(params), grad_alpha.data_ptr(), first, K, s_first, s_last,
+                                                             C.byref(ptrs), x0, y0, x1, y1, self._stream()))
         return into
 
     def _segment_inputs(self, what, params, rays, t_near, t_far, T_in, window):

@@ -175,18 +175,30 @@ def particle_stats(tracer, params, rays=None, ray_weight=None, into=None, steps=
         return tracer.particle_stats(params, rays=rays, ray_weight=ray_weight, into=into)
 
 
-def ray_picks(tracer, params, rays=None, window=None, cross_T=0.5, picks=grt.PICK_RULES, fields=grt.PICK_FIELDS):
+def ray_picks(tracer, params, rays=None, window=None, cross_T=0.5, picks=grt.PICK_RULES, fields=None, through_meshes=False, steps=None):
     """Per-ray picks of the frame (or of its `window`, or of `rays` [n][6]) under torch.no_grad(): {pick: {field: tensor}} for the
     picks 'first', 'peak' and 'cross' and the fields 'id' (uint32, grt.PICK_NONE where the ray has no such event), 't' and 'weight'
     (Tracer.ray_picks; include/grt.h: grt_ray_picks_frame / grt_ray_picks_rays) — which particle every ray sees first, strongest and
     where its transmittance falls to cross_T (0.5: the median depth), for picking, lasso selection, id maps and surface depth.
     Like particle_stats it reads the scene the tracer HOLDS and uploads nothing: call it right after grt_torch.render(tracer, ...).
     The picks are discrete: nothing here is differentiable, the tensors carry no graph, and `rays` that requires grad is refused
-    (ValueError), as render_features refuses it."""
+    (ValueError), as render_features refuses it.
+    through_meshes=True sends the call to Tracer.ray_picks_mesh (grt_ray_picks_mesh_*): the rays
+    bounce as the frame's do, every pick has the further fields 'step' (the 1-based iteration it was met in) and 'point' (its world
+    position on that iteration's ray, [..][3]), and only the events of the iterations first .. last are candidates (1-based,
+    inclusive, last None = open): (2, None) picks what is seen only through a bounce.  The flag alone is the switch: without it the
+    call is today's, a tracer with meshes is refused as before (GrtError: ray picks are computed for Gaussian-only frames), and `steps`
+    given without it raises ValueError."""
     if rays is not None and rays.requires_grad:
         raise ValueError("grt_torch.ray_picks: picks are discrete and carry no gradient with respect to rays; detach rays")
+    mesh = bool(through_meshes)
+    if steps is not None and not mesh:
+        raise ValueError("grt_torch.ray_picks: steps is an argument of the mesh call; pass through_meshes=True with it")
     with torch.no_grad():
-        return tracer.ray_picks(params, rays=rays, window=window, cross_T=cross_T, picks=picks, fields=fields)
+        if mesh:
+            return tracer.ray_picks_mesh(params, rays=rays, window=window, cross_T=cross_T, picks=picks,
+                                         fields=grt.MESH_PICK_FIELDS if fields is None else fields, steps=steps)
+        return tracer.ray_picks(params, rays=rays, window=window, cross_T=cross_T, picks=picks, fields=grt.PICK_FIELDS if fields is None else fields)
 
 
 class _RayEvents(torch.autograd.Function):
@@ -216,7 +228,38 @@ class _RayEvents(torch.autograd.Function):
         return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 6
 
 
-def ray_events(tracer, params, geometry=None, rays=None, window=None, max_events=32, first=0):
+class _RayEventsMesh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, scale, quat, opacity, rays, window, tracer, params, max_events, first, steps, max_steps):
+        # pos .. opacity: the tensors of the tracer's last upload: only the carriers of the geometry gradients
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.params, ctx.window, ctx.first, ctx.steps = tracer, params, window, first, steps
+        ctx.rays = rays.detach() if rays is not None else None
+        ctx.like = tuple((t.device, t.dtype) for t in (pos, scale, quat, opacity))
+        out = tracer.ray_events_mesh(params, rays=ctx.rays, window=window, max_events=max_events, first=first, steps=steps, max_steps=max_steps)
+        names = tuple(k for k in grt.MESH_EVENT_FIELDS + grt.MESH_PATH_FIELDS if k in out)
+        ctx.n_out = len(names)
+        ctx.at_alpha = names.index("alpha")
+        ctx.mark_non_differentiable(*(out[k] for k in names if k != "alpha"))
+        return tuple(out[k] for k in names)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("pos", "scale", "quat", "opacity")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:4]) if want]
+        g_alpha = gs[ctx.at_alpha]
+        if not groups or g_alpha is None:
+            return (None,) * 12
+        g = tr.backward_events_mesh(ctx.params, g_alpha, rays=ctx.rays, window=ctx.window, first=ctx.first, groups=groups, steps=ctx.steps)
+        return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 8
+
+
+def ray_events(tracer, params, geometry=None, rays=None, window=None, max_events=32, first=0, through_meshes=False, steps=None, max_steps=0):
     """Every ray's own list of composited events (Tracer.ray_events; include/grt.h: grt_ray_events_frame / _rays): a dict of 'id', 't',
     'alpha' [K][h][w] (or [K][n] for `rays` [n][6]; K = max_events, the events first .. first + K - 1 in compositing order, slot-major)
     and 'count', 'T_in' [h][w] (or [n]) on the tracer's GPU.  With T = T_in * cumprod(1 - alpha, 0) the transmittances behind the
@@ -230,13 +273,26 @@ def ray_events(tracer, params, geometry=None, rays=None, window=None, max_events
     grt_torch.ray_events(tracer, ...) can share one loss.backward().  The `geometry` tensors only carry the gradient — they must be
     the tensors of the tracer's last upload, their shapes are checked against the tracer's particle count and their values are not
     read.  The backward raises GrtError when the tracer has received another upload since the forward.  Gradients with respect to
-    rays are not computed (`rays` that requires grad: ValueError), and neither are mesh frames (a tracer with meshes: ValueError)."""
-    if tracer.has_meshes:
-        raise ValueError("grt_torch.ray_events: meshes are set on this tracer; ray events are listed for Gaussian-only frames")
+    rays are not computed (`rays` that requires grad: ValueError).
+    through_meshes=True sends the call to Tracer.ray_events_mesh / backward_events_mesh
+    (grt_ray_events_mesh_*, grt_backward_events_mesh_*): the rays bounce as the frame's do; the events of the iterations first .. last
+    (1-based, inclusive, last None = open; (2, None): what is seen only through a bounce) are numbered over the whole ray and listed
+    with a further 'step' [K][..]; max_steps = P > 0 adds the path 'path_rays' [P][..][6], 'path_t_far', 'path_state' [P][..] and
+    'n_steps' [..].  'alpha' carries the graph to the four geometry tensors, differentiated on each iteration's own ray with the
+    meshes held fixed; 'step', 'id', 't', 'T_in', 'count' and the path are data.  The flag alone is the switch: without it the call is
+    today's, a tracer with meshes raises ValueError as before, and so do `steps` or `max_steps` given without it."""
+    mesh = bool(through_meshes)
+    if (steps is not None or max_steps) and not mesh:
+        raise ValueError("grt_torch.ray_events: steps and max_steps are arguments of the mesh call; pass through_meshes=True with them")
+    if tracer.has_meshes and not mesh:
+        raise ValueError("grt_torch.ray_events: meshes are set on this tracer; ray events are listed for Gaussian-only frames "
+                         "(pass through_meshes=True to list them through the bounces)")
     if rays is not None and rays.requires_grad:
         raise ValueError("grt_torch.ray_events: gradients with respect to rays are not computed through the event list; detach rays")
     if geometry is None:
         with torch.no_grad():
+            if mesh:
+                return tracer.ray_events_mesh(params, rays=rays, window=window, max_events=max_events, first=first, steps=steps, max_steps=max_steps)
             return tracer.ray_events(params, rays=rays, window=window, max_events=max_events, first=first)
     geo = tuple(geometry)
     scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene)
@@ -248,6 +304,9 @@ def ray_events(tracer, params, geometry=None, rays=None, window=None, max_events
         if tuple(t.shape) != shape:
             raise ValueError(f"grt_torch.ray_events: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
                              f"not {tuple(t.shape)}")
+    if mesh:
+        out = _RayEventsMesh.apply(*geo, rays, window, tracer, params, max_events, first, steps, max_steps)
+        return dict(zip(grt.MESH_EVENT_FIELDS + (grt.MESH_PATH_FIELDS if max_steps else ()), out))
     out = _RayEvents.apply(*geo, rays, window, tracer, params, max_events, first)
     return dict(zip(grt.EVENT_FIELDS, out))
 

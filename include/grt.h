@@ -629,8 +629,8 @@ GRT_API int grt_particle_stats_rays(grt_ctx* ctx, const grt_params* p, const flo
  * On a scene WITHOUT meshes a ray has one last pass: count, weight_max and weight_sum are the plain call's, cw_i = (1 - T_end) w_i.
  * Refused with GRT_ERR_INVALID like the plain call, without its meshes row: GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a
  * window outside the frame, sh_degree_max > 3, t_min <= 0; and p->type outside MIRROR/NORMAL/GLASS, step_first > step_last with
- * step_last != 0.  GRT_ERR_LIMIT as in the backward.  Not computed on mesh frames: picks, event lists (feature channels:
- * grt_render_features_mesh_frame, below). */
+ * step_last != 0.  GRT_ERR_LIMIT as in the backward.  (Feature channels of mesh frames: grt_render_features_mesh_frame; picks and
+ * event lists: grt_ray_picks_mesh_frame, grt_ray_events_mesh_frame, below.) */
 typedef struct {
     float* weight_sum;
     float* weight_max;
@@ -731,7 +731,8 @@ GRT_API int grt_backward_features_rays(grt_ctx* ctx, const grt_params* p, const 
  * meshes row: NULL p, no BVH, GRT_OPT_COUNTERS = 1, sh_degree_max > 3, t_min <= 0, a window outside the frame, a NULL ray buffer,
  * channels 0 or above GRT_MAX_FEATURE_CHANNELS, a NULL feat, output or upstream; and p->type outside MIRROR/NORMAL/GLASS,
  * step_first > step_last with step_last != 0.  GRT_ERR_LIMIT as in the mesh backward (the LDS stack of the higher of the two trees).
- * Not computed: picks and event lists on mesh frames, gradients with respect to rays, camera or meshes, a feature of the surface. */
+ * Not computed: gradients with respect to rays, camera or meshes, a feature of the surface.  (Picks and event lists of mesh frames:
+ * grt_ray_picks_mesh_frame, grt_ray_events_mesh_frame, below.) */
 GRT_API int grt_render_features_mesh_frame(grt_ctx* ctx, const grt_params* p, const float* d_feat, uint32_t channels, float* d_out,
                                            uint32_t step_first, uint32_t step_last, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
                                            void* stream);
@@ -770,7 +771,8 @@ GRT_API int grt_backward_features_mesh_rays(grt_ctx* ctx, const grt_params* p, c
  * grt_particle_stats_* refuses (GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a window outside the frame, sh_degree_max > 3,
  * t_min <= 0), meshes set (ray picks are computed for Gaussian-only frames), all nine pointers NULL, cross_T outside (0, 1) (NaN
  * included) while any array of `cross` is requested.  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks exceed 160 KiB, as
- * in the statistics.  Not computed: more than one pick per rule, gradients of any kind, mesh frames. */
+ * in the statistics.  Not computed: more than one pick per rule, gradients of any kind.  Mesh frames have calls of their own
+ * (grt_ray_picks_mesh_frame, below). */
 #define GRT_PICK_NONE 0xFFFFFFFFu
 typedef struct {
     uint32_t* id;
@@ -825,7 +827,8 @@ GRT_API int grt_ray_picks_rays(grt_ctx* ctx, const grt_params* p, const float* d
  * buffer), meshes set (ray events are listed for Gaussian-only frames), max_events = 0, first + max_events overflowing 32 bits, no
  * output (forward: out NULL or all five arrays NULL; backward: out NULL or pos, scale, quat and opacity all NULL), a NULL upstream,
  * out->sh != NULL (colour does not depend on the listed quantities).  GRT_ERR_LIMIT: a BVH so high that its per-lane LDS stacks
- * exceed 160 KiB, as in the backward.  Not computed: gradients through t_i, gradients with respect to rays or the camera, mesh frames. */
+ * exceed 160 KiB, as in the backward.  Not computed: gradients through t_i, gradients with respect to rays or the camera.  Mesh frames
+ * have calls of their own (grt_ray_events_mesh_frame, below). */
 typedef struct grt_ray_events {
     uint32_t* id;    /* [K][N] */
     float* t;        /* [K][N] */
@@ -841,6 +844,94 @@ GRT_API int grt_backward_events_frame(grt_ctx* ctx, const grt_params* p, const f
                                       const grt_gaussian_grads* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_backward_events_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_alpha,
                                      uint32_t first, uint32_t max_events, const grt_gaussian_grads* out, void* stream);
+/* ---- per-ray picks and event lists of MESH frames: what a ray sees through mirrors and glass ----
+ * The two per-ray queries above for a scene with meshes set (grt_set_meshes): rays bounce as grt_render / grt_render_aux trace them.
+ * A ray runs iterations s = 1..S exactly as documented at grt_backward_mesh, each on its own ray (o_s, d_s): ONE event list with ONE
+ * running transmittance carried across segments through `density` (the start of a step is T = 1 - density, two float32 roundings).
+ * A COMPOSITED EVENT is exactly the mesh backward's; its weight is w_i = T_i alpha_i, T_i the running transmittance BEFORE the event,
+ * one float32 product — the w_i of grt_particle_stats_mesh.
+ *   step_first, step_last   as for grt_particle_stats_mesh: the iterations whose events are candidates (picks) or are numbered and
+ *                  listed (event lists), 1-based, inclusive; 0, 0 = all; step_last = 0 leaves the range open.  Events outside the
+ *                  range are still composited: T, A and B run through them.  (2, 0): what is seen only through a bounce.
+ * The colour weight c_s w_i is NOT used by either query: it needs a second walk (D_S is known only behind the last segment), and
+ * grt_particle_stats_mesh already reports it; alpha, step and path_state of the event list let a caller rebuild A, B and c_s.
+ * PICKS.  The rules of grt_ray_picks among the events inside the step range: first — the first such event; peak — the largest w_i,
+ * replaced only by a STRICTLY greater weight; cross — the first such event with T_i (1 - alpha_i) <= cross_T, T the ray's OWN running
+ * transmittance, not one restarted at the range.  Per rule:
+ *     id       the particle's ORIGINAL id                          weight   w_i
+ *     t        the key distance along the iteration's own ray,     step     the 1-based iteration s
+ *              in units of |d_s|                                   point    [N][3]: o_s[k] + t * d_s[k], one float32 multiplication
+ *                                                                           and one addition per component, no contraction
+ * "None" — a ray with no such event, a ray that is not traced — is GRT_PICK_NONE, 0.0f, 0.0f, 0, (0, 0, 0).  Every element of the
+ * window or of the buffer is WRITTEN exactly once per requested array; each of the fifteen arrays may be NULL.  No atomic and no
+ * buffer of the context: BITWISE reproducible, windows tile a frame bit for bit, a frame rendered after the call is bit-identical to
+ * one rendered before it, a view computes its scene's result.  On a scene WITHOUT meshes, with steps 0, 0, id, t and weight are
+ * grt_ray_picks' bytes and step is 1.
+ * Refused with GRT_ERR_INVALID as grt_particle_stats_mesh_* (GRT_OPT_COUNTERS = 1, no BVH, NULL p / out / rays, a window outside the
+ * frame, sh_degree_max > 3, t_min <= 0, p->type outside MIRROR/NORMAL/GLASS, step_first > step_last with step_last != 0), and: all
+ * fifteen pointers NULL, cross_T outside (0, 1) (NaN included) while any array of `cross` is requested.  GRT_ERR_LIMIT as in the mesh
+ * backward (the LDS stack of the higher of the two trees). */
+typedef struct {
+    uint32_t* id;
+    float* t;
+    float* weight;
+    uint32_t* step;
+    float* point; /* [N][3] */
+} grt_pick_mesh_out; /* each may be NULL */
+typedef struct {
+    grt_pick_mesh_out first, peak, cross;
+    float cross_T;
+    uint32_t step_first, step_last;
+} grt_ray_picks_mesh;
+GRT_API int grt_ray_picks_mesh_frame(grt_ctx* ctx, const grt_params* p, const grt_ray_picks_mesh* out, uint32_t x0, uint32_t y0,
+                                     uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_ray_picks_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_ray_picks_mesh* out,
+                                    void* stream);
+/* EVENT LISTS.  FORWARD: the events inside the step range are numbered 0, 1, ... in compositing order over the WHOLE ray; events
+ * first .. first + K - 1 go to slot n - first of id, t, alpha (as grt_ray_events) and step (the 1-based iteration; t is measured on
+ * that iteration's ray).  count is ALL events inside the range; T_in the running float32 T in front of event `first` — the T behind
+ * the ray's last segment when count <= first, 1 for a ray that is not traced.  Unused slots hold GRT_PICK_NONE, 0, 0, 0.
+ * The PATH: slot s - 1 of path_rays / path_t_far / path_state holds iteration s — its ray, the end of its segment (the mesh hit
+ * distance, or t_max) and its state —, whatever the step range; with them (step, t) becomes a world position and A, B and c_s can be
+ * rebuilt from alpha.  Iterations beyond max_steps are not stored; n_steps counts them all.  Unused path slots hold zeros and
+ * GRT_PICK_NONE.  All stores are plain: BITWISE reproducible, windows tile, pages (first = 0, K, 2K, ...) concatenate.  On a scene
+ * WITHOUT meshes, with steps 0, 0, id, t, alpha, count and T_in are grt_ray_events' bytes.
+ * BACKWARD.  d_grad_alpha [K][N] for the same first, max_events and step range: dloss/dalpha of the listed event.  The call ADDS
+ * sum g * d alpha_i / d (pos, scale, quat, opacity) into the caller's arrays, alpha_i differentiated on THE ITERATION'S OWN RAY
+ * (o_s, d_s), the mesh hits, normals and next rays held fixed; nothing where the 0.99 clamp binds; a ray whose K upstream values are
+ * all exactly 0 is not traced.  ONE traversal, through the gradient buffer and its flush as grt_backward; float atomics
+ * (GRT_OPT_BWD_PLAIN_ATOMICS applies).
+ * Refused with GRT_ERR_INVALID as grt_ray_events_* / grt_backward_events_* with the meshes row replaced by the mesh calls' own
+ * (p->type outside MIRROR/NORMAL/GLASS), and: step_first > step_last with step_last != 0, max_steps = 0 while a path array is given,
+ * (backward) out->sh != NULL, no geometry group, a NULL upstream.  GRT_ERR_LIMIT as in the mesh backward.  Not computed: picks by
+ * colour weight, gradients through t_i, through the path, or with respect to rays, camera or meshes. */
+#define GRT_STEP_LAST 0u      /* the last Gaussian pass: the ray met no mesh, or max_bounces is spent */
+#define GRT_STEP_GAUSSIAN 1u  /* a Gaussian pass: the segment ends at a mesh hit that bounces */
+#define GRT_STEP_TERMINATE 3u /* the segment ends at a GRT_NORMAL hit */
+typedef struct grt_ray_events_mesh {
+    uint32_t* id;    /* [K][N], slot-major as grt_ray_events */
+    float* t;        /* [K][N] */
+    float* alpha;    /* [K][N] */
+    uint32_t* step;  /* [K][N] */
+    uint32_t* count; /* [N] */
+    float* T_in;     /* [N] */
+    uint32_t first, max_events, step_first, step_last;
+    float* path_rays;     /* [P][N][6]: (o_s, d_s) of iteration s = slot + 1 */
+    float* path_t_far;    /* [P][N]: the segment's end (mesh hit distance, or t_max) */
+    uint32_t* path_state; /* [P][N]: GRT_STEP_LAST, GRT_STEP_GAUSSIAN, GRT_STEP_TERMINATE; GRT_PICK_NONE unused */
+    uint32_t* n_steps;    /* [N]: ALL iterations the ray ran, not capped by P */
+    uint32_t max_steps;   /* P; may be 0 when no path array is given */
+} grt_ray_events_mesh;
+GRT_API int grt_ray_events_mesh_frame(grt_ctx* ctx, const grt_params* p, const grt_ray_events_mesh* out, uint32_t x0, uint32_t y0,
+                                      uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_ray_events_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const grt_ray_events_mesh* out,
+                                     void* stream);
+GRT_API int grt_backward_events_mesh_frame(grt_ctx* ctx, const grt_params* p, const float* d_grad_alpha, uint32_t first, uint32_t max_events,
+                                           uint32_t step_first, uint32_t step_last, const grt_gaussian_grads* out, uint32_t x0, uint32_t y0,
+                                           uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_events_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, const float* d_grad_alpha,
+                                          uint32_t first, uint32_t max_events, uint32_t step_first, uint32_t step_last,
+                                          const grt_gaussian_grads* out, void* stream);
 /* ---- ray segments: per-ray range and carried transmittance, with gradients ----
  * Every call above renders a WHOLE ray: one t_min / t_max for all rays, transmittance 1 at the start, the reference's pixel rad * A.
  * These calls are the reference's trace() itself (shaders/tracer.cuh:328-373): ONE segment [t_near, t_far] of every ray, entered with
