@@ -26,6 +26,14 @@ reference walk; every test that holds a walk measures it again and asserts (figu
 scene's own figure.  MEASURED_FRAGILE: the fragile rays of every scene by the walk's margin alone.
 
 FAULTS: seeded mistakes the comparisons must name (tests/test_mesh_event_check.py).
+
+The device's backward scans a lane's column of the upstream before it walks and leaves the walk at the end of the round that holds
+the lane's last non-zero slot s_last: it compares first + s_last + 1 with the number of the lane's events inside `steps` so far.
+sparse_upstream() makes the columns that exercise it (a loss on a few events, one live lane in a wave, one live wave), CASES names
+every such upstream the device tests use — pages of a long call, a window, the updated scene among them —, MEASURED_F32_CASES holds
+each case's own float32 figure (a sparse upstream has a smaller scale: the dense figure is not borrowed), and STOP_FAULTS are that
+path's mistakes: leaves_at_first_zero_slot (the scan stops at the first zero slot), stop_ignores_first (s_last + 1 without first),
+stop_counts_all_steps (compared with the event's number over all steps).
 """
 import functools
 
@@ -43,8 +51,11 @@ FIELDS = ("id", "t", "alpha", "step", "count", "T_in")
 PATH_FIELDS = ("path_rays", "path_t_far", "path_state", "n_steps")
 GROUPS = E.GROUPS
 FORWARD_FAULTS = ("slot_counts_all_steps", "path_slot_offset", "tail_not_filled")
-BACKWARD_FAULTS = ("camera_ray_in_chain", "clamp_ignored", "upstream_past_count")
+STOP_FAULTS = ("leaves_at_first_zero_slot", "stop_ignores_first", "stop_counts_all_steps")
+CHAIN_FAULTS = ("camera_ray_in_chain", "clamp_ignored", "upstream_past_count")
+BACKWARD_FAULTS = CHAIN_FAULTS + STOP_FAULTS
 FAULTS = FORWARD_FAULTS + BACKWARD_FAULTS
+ROUND = 7  # events of one k-nearest round: a lane tests whether to leave its walk between two rounds
 
 # the longest list of every scene (all steps), and the K of its tests: the smallest multiple of 16 that holds it; 32 on glass and hall
 # (truncated lists, pages)
@@ -215,7 +226,9 @@ def upstream(scene, ev, K, first=0):
 
 def event_upstream(g, ev, first=0, steps=None, fault=None):
     """[E] float32: the upstream value of every event — g[slot][ray] for a listed event, 0 for the others.  fault upstream_past_count:
-    a kernel that clamps the slot to the ray's last event hands that event the values behind it as well."""
+    a kernel that clamps the slot to the ray's last event hands that event the values behind it as well.  STOP_FAULTS: a lane that
+    leaves its walk at a wrong event number w (module docstring) — it still finishes the round of seven that holds event w - 1, so
+    exactly the events numbered >= w + 6 are dropped and every other one is kept."""
     K = g.shape[0]
     s, inside = slots(ev, first, steps)
     listed = inside & (s >= 0) & (s < K)
@@ -228,6 +241,21 @@ def event_upstream(g, ev, first=0, steps=None, fault=None):
             if len(li) and 0 < c < K:
                 e = es.start + int(li[-1])
                 out[e] = f32(out[e] + g[c:, r].sum(dtype=f32))
+    if fault in STOP_FAULTS:
+        nz = g != 0
+        for r, es, _ in ev.by_ray():
+            col = nz[:, r]
+            if not col.any():
+                continue
+            if fault == "leaves_at_first_zero_slot":
+                if col.all():
+                    continue
+                w = first + int(np.argmin(col))
+            else:
+                s_last = int(np.nonzero(col)[0][-1])
+                w = s_last + 1 if fault == "stop_ignores_first" else first + s_last + 1
+            number = np.arange(es.stop - es.start) if fault == "stop_counts_all_steps" else s[es] + first
+            out[es][number >= w + ROUND - 1] = 0
     return out
 
 
@@ -262,3 +290,203 @@ def measure_f32(parts, ev, g_ev):
         for k, v in G.error_over_scale(got, want, scale).items():
             out[k] = max(out[k], v)
     return out
+
+
+# ---- sparse upstreams, pages, windows: the upstreams a caller's loss really hands over (DESIGN.md 5.24) ----
+def counts(ev, steps=None):
+    """[n_rays] int64: every ray's events inside the step range."""
+    _, inside = slots(ev, 0, steps)
+    return np.bincount(ev.ray[inside], minlength=ev.n_rays)
+
+
+def wave_mask(scene, ev, pattern):
+    """([n_rays] bool, ray): tests/test_gpu_mesh_grad_edges._sparse_mask's rays — one lane per wave (`one_per_tile`) or one whole wave
+    (`one_tile`), placed on the sturdy ray of the most steps that has events in two segments or more.  A wave of a camera frame is an
+    8 x 8 tile of pixels, a wave of a ray buffer 64 consecutive rays."""
+    import mesh_grad_scenes as S
+    st = S.stats(ev)
+    longest = int(np.argmax(st["steps"] * (ev.margin >= G.FRAGILE_REL) * (st["segs_with"] >= 2)))
+    m = np.zeros(ev.n_rays, bool)
+    if scene["camera"]:
+        w = scene["p"].width
+        y, x = divmod(longest, w)
+        m2 = m.reshape(-1, w)
+        if pattern == "one_per_tile":
+            m2[y % 8::8, x % 8::8] = True
+        else:
+            m2[y - y % 8:y - y % 8 + 8, x - x % 8:x - x % 8 + 8] = True
+    elif pattern == "one_per_tile":
+        m[longest % 64::64] = True
+    else:
+        m[longest - longest % 64:longest - longest % 64 + 64] = True
+    return m, longest
+
+
+def sparse_upstream(scene, ev, K, pattern, first=0, steps=None):
+    """(g [K][n_rays] float32, number of fragile rays silenced): upstream()'s seeded values (the same generator, without the zero
+    column on every eighth ray), the fragile rays' columns zero, masked to one of SPARSE_PATTERNS.  With c the ray's events inside
+    `steps` minus first, cut to K:
+    head          slot 0 only;
+    last          slot c - 1 only (c <= 0: a zero column) — the lane walks its whole list with nothing to do before the end;
+    one_mid       one slot drawn uniformly from [0, c);
+    holes         every slot kept with probability 1/3, and everything from a cut drawn uniformly from [1, c] onwards zero: the last
+                  non-zero slot has zeros in front of it;
+    one_per_tile, one_tile   dense columns on wave_mask()'s rays only.
+    The masks come from a generator of their own, seeded by the scene, the pattern, K and first."""
+    n = ev.n_rays
+    base, n_sil = upstream(scene, ev, K, first)
+    g = np.random.default_rng(sum(map(ord, scene["name"])) + 1000 * K + first).normal(size=(K, n)).astype(f32)
+    assert np.array_equal(g[base != 0], base[base != 0])  # (event_check.upstream's values)
+    g[:, fragile(ev)] = 0
+    c = np.clip(counts(ev, steps) - first, 0, K)
+    rng = np.random.default_rng(sum(map(ord, scene["name"] + pattern)) + 1000 * K + first)
+    keep = np.zeros((K, n), bool)
+    has = c > 0
+    if pattern == "head":
+        keep[0] = True
+    elif pattern == "last":
+        keep[c[has] - 1, np.nonzero(has)[0]] = True
+    elif pattern == "one_mid":
+        at = np.minimum((rng.random(n) * c).astype(np.int64), np.maximum(c - 1, 0))
+        keep[at[has], np.nonzero(has)[0]] = True
+    elif pattern == "holes":
+        cut = 1 + np.minimum((rng.random(n) * c).astype(np.int64), np.maximum(c - 1, 0))
+        keep = (rng.random((K, n)) < 1.0 / 3.0) & (np.arange(K)[:, None] < np.where(has, cut, 0)[None, :])
+    elif pattern in ("one_per_tile", "one_tile"):
+        keep[:, wave_mask(scene, ev, pattern)[0]] = True
+    else:
+        raise ValueError(pattern)
+    return np.where(keep, g, f32(0)), n_sil
+
+
+SPARSE_PATTERNS = ("head", "last", "one_mid", "holes", "one_per_tile", "one_tile")
+WINDOW = (5, 3, 19, 14)  # of hall_cap4's 32 x 24: no multiple of 8
+UPDATED = "mirror_updated"
+
+# every upstream the device tests use beside upstream(scene, ev, BACKWARD_K[scene]):
+# key -> (scene, pattern, K, first, steps).  Patterns beside SPARSE_PATTERNS: `dense` upstream(scene, ev, K); `rows_of_L` the rows
+# first .. first + K - 1 of upstream(scene, ev, L) (a page of the long call); `window` dense, zero outside WINDOW; `slot_3` 1 in slot 3
+# and 0 elsewhere (what autograd hands over for the loss alpha[3].sum()), the fragile rays' columns zero.
+CASES = {
+    "mirror/head": ("mirror", "head", 144, 0, None), "mirror/last": ("mirror", "last", 144, 0, None),
+    "mirror/one_mid": ("mirror", "one_mid", 144, 0, None), "mirror/holes": ("mirror", "holes", 144, 0, None),
+    "mirror/last/behind": ("mirror", "last", 144, 0, X.BEHIND),
+    "glass/one_mid": ("glass", "one_mid", 32, 0, None), "glass/holes": ("glass", "holes", 32, 0, None),
+    "glass/one_per_tile/behind": ("glass", "one_per_tile", 32, 0, X.BEHIND), "glass/one_tile/behind": ("glass", "one_tile", 32, 0, X.BEHIND),
+    "ragged_mesh_rays/one_per_tile": ("ragged_mesh_rays", "one_per_tile", 144, 0, None),
+    "ragged_mesh_rays/one_tile": ("ragged_mesh_rays", "one_tile", 144, 0, None),
+    "glass/long_96": ("glass", "dense", 96, 0, None),
+    "glass/page_0": ("glass", "rows_of_96", 32, 0, None), "glass/page_32": ("glass", "rows_of_96", 32, 32, None),
+    "glass/page_64": ("glass", "rows_of_96", 32, 64, None),
+    "mirror/behind/long_144": ("mirror", "dense", 144, 0, X.BEHIND),
+    "mirror/behind/page_0": ("mirror", "rows_of_144", 72, 0, X.BEHIND), "mirror/behind/page_72": ("mirror", "rows_of_144", 72, 72, X.BEHIND),
+    "glass/last/first_32": ("glass", "last", 32, 32, None),
+    "hall_cap4/window": ("hall_cap4", "window", 80, 0, None),
+    "mirror/slot_3/behind": ("mirror", "slot_3", 8, 0, X.BEHIND),
+    UPDATED + "/dense": (UPDATED, "dense", 144, 0, None),
+}
+# float32 evaluation against float64, error / scale per group, of every case above (measure_f32 on case(key)'s upstream; measured on
+# the CPU from the reference walk, measured again by tests/test_mesh_event_check.py; the device is held to 4 x max(figure, 2^-23))
+MEASURED_F32_CASES = {
+    "mirror/head": {"pos": 2.51e-05, "scale": 4.34e-05, "quat": 4.49e-05, "opacity": 7.53e-07},
+    "mirror/last": {"pos": 2.83e-4, "scale": 2.81e-4, "quat": 8.05e-05, "opacity": 1.04e-06},
+    "mirror/one_mid": {"pos": 1.25e-4, "scale": 1.17e-4, "quat": 9.57e-05, "opacity": 1.22e-06},
+    "mirror/holes": {"pos": 4.68e-4, "scale": 1.23e-4, "quat": 1.87e-4, "opacity": 1.64e-06},
+    "mirror/last/behind": {"pos": 2e-05, "scale": 2.92e-05, "quat": 1.85e-05, "opacity": 7.48e-07},
+    "glass/one_mid": {"pos": 1.12e-4, "scale": 1.73e-4, "quat": 4.89e-05, "opacity": 1.73e-06},
+    "glass/holes": {"pos": 2.82e-4, "scale": 1.7e-4, "quat": 2.19e-4, "opacity": 1.07e-06},
+    "glass/one_per_tile/behind": {"pos": 1.38e-05, "scale": 1.86e-05, "quat": 6.93e-06, "opacity": 2.52e-07},
+    "glass/one_tile/behind": {"pos": 2.5e-05, "scale": 1.86e-05, "quat": 1.43e-05, "opacity": 3.41e-07},
+    "ragged_mesh_rays/one_per_tile": {"pos": 3.02e-05, "scale": 1.2e-05, "quat": 2.06e-05, "opacity": 1.11e-06},
+    "ragged_mesh_rays/one_tile": {"pos": 2.14e-05, "scale": 1.05e-05, "quat": 1.63e-05, "opacity": 5.26e-07},
+    "glass/long_96": {"pos": 2.04e-4, "scale": 2.39e-4, "quat": 9.48e-05, "opacity": 1.67e-06},
+    "glass/page_0": {"pos": 2.04e-4, "scale": 2.39e-4, "quat": 9.48e-05, "opacity": 1.83e-06},
+    "glass/page_32": {"pos": 1.77e-4, "scale": 8.4e-05, "quat": 4.74e-05, "opacity": 1.21e-06},
+    "glass/page_64": {"pos": 1.88e-4, "scale": 1.57e-4, "quat": 4.27e-4, "opacity": 9.62e-07},
+    "mirror/behind/long_144": {"pos": 3.39e-05, "scale": 2.92e-05, "quat": 1.93e-05, "opacity": 7.63e-07},
+    "mirror/behind/page_0": {"pos": 3.39e-05, "scale": 2.92e-05, "quat": 1.93e-05, "opacity": 7.1e-07},
+    "mirror/behind/page_72": {"pos": 8.42e-06, "scale": 1.25e-05, "quat": 4.47e-06, "opacity": 7.56e-07},
+    "glass/last/first_32": {"pos": 4.36e-05, "scale": 5e-05, "quat": 2.24e-05, "opacity": 1.06e-06},
+    "hall_cap4/window": {"pos": 1.64e-4, "scale": 3.36e-4, "quat": 9.21e-05, "opacity": 8.09e-07},
+    "mirror/slot_3/behind": {"pos": 1.77e-05, "scale": 4.29e-05, "quat": 1.68e-05, "opacity": 9.33e-07},
+    UPDATED + "/dense": {"pos": 1.13e-4, "scale": 1.08e-4, "quat": 1e-4, "opacity": 5.78e-07},
+}
+
+
+# the tolerance of the updated scene's lists (alpha, T_in): mesh_stats_check.measure_f32 with mesh_stats_check.ray_weights on ITS
+# walk, the maximum over the four float outputs (colour_max), as mesh_pick_check.MEASURED_F32_MORE holds the off-centre glass scene's
+MEASURED_F32_WEIGHT = {UPDATED: 1.46e-6}
+
+
+def weight_tol_of_updated():
+    return 4 * max(MEASURED_F32_WEIGHT[UPDATED], 2.0 ** -23)
+
+
+@functools.lru_cache(maxsize=None)
+def walked_updated():
+    """`mirror` after tests/test_gpu_mesh_grad_edges' two updates — its moved Gaussians and its moved, tilted plane — walked by
+    PickWalker (that file's updated() walks with MeshWalker: no event distances) and proven on the new values.  Computed once per run
+    and never changed by the tests."""
+    import mesh_grad_scenes as S
+    import oracle as O
+    import test_gpu_mesh_grad_edges as GE
+    from common import acts_to_particles
+    s = S.build("mirror")
+    s["sc"].close()
+    s["name"] = UPDATED
+    s["acts"] = GE._moved_acts(s["acts"])
+    s["parts"] = acts_to_particles(s["acts"])
+    s["mesh"] = GE._moved_plane(s["mesh"])
+    s["meshes"] = [s["mesh"]]
+    s["sc"] = O.Scene(s["parts"], s["alpha_min"])
+    s["sc"].set_mesh(*s["mesh"])
+    s["ev"] = X.PickWalker(s["parts"], s["op"], s["sc"], s["mesh"]).walk(s["rays"], s["live"], camera=True)
+    s["n_traced"] = int(S.traced(s["rays"], s["live"]).sum())
+    return s
+
+
+def scene_of(name):
+    """The walked scene of a case: mesh_pick_check.walked's cached one, or walked_updated()."""
+    return walked_updated() if name == UPDATED else X.walked(name)
+
+
+@functools.lru_cache(maxsize=None)
+def case(key):
+    """{s, ev, g [K][n_rays], g_ev [E], first, steps, n_silenced, want, scale} of CASES[key]: computed once per run, shared by the
+    tests that need it and never changed by them."""
+    name, pattern, K, first, steps = CASES[key]
+    s = scene_of(name)
+    ev = s["ev"]
+    if pattern in SPARSE_PATTERNS:
+        g, n_sil = sparse_upstream(s, ev, K, pattern, first, steps)
+    elif pattern.startswith("rows_of_"):
+        g, n_sil = upstream(s, ev, int(pattern[8:]))
+        g = g[first:first + K]
+    elif pattern == "slot_3":
+        g = np.zeros((K, ev.n_rays), f32)
+        g[3, ~fragile(ev)] = 1
+        n_sil = int(fragile(ev).sum())
+    else:
+        g, n_sil = upstream(s, ev, K, first)
+        if pattern == "window":
+            x0, y0, x1, y1 = WINDOW
+            m = np.zeros((s["p"].height, s["p"].width), bool)
+            m[y0:y1, x0:x1] = True
+            g = g * m.reshape(-1)
+    g_ev = event_upstream(g, ev, first, steps)
+    want, scale = evaluate_backward(s["parts"], ev, g_ev)
+    return dict(s=s, ev=ev, g=g, g_ev=g_ev, first=first, steps=steps, n_silenced=n_sil, want=want, scale=scale)
+
+
+def tol_of_case(key):
+    """{group: 4 x max(the case's own float32 figure, 2^-23)}: a sum of one event per particle has almost no rounding of its own,
+    while the device forms an event's terms in another order (tests/test_gpu_mesh_grad_edges.updated's floor)."""
+    return {k: 4 * max(v, 2.0 ** -23) for k, v in MEASURED_F32_CASES[key].items()}
+
+
+def stop_of(g, ev, first=0, steps=None):
+    """([n_rays] int64 s_last — the ray's last non-zero slot, -1 for a zero column —, [n_rays] int64 the ray's events inside `steps`):
+    a lane of the backward leaves its walk behind event first + s_last; where first + s_last < count that is before its list ends."""
+    nz = g != 0
+    s_last = np.where(nz.any(0), g.shape[0] - 1 - np.argmax(nz[::-1], axis=0), -1)
+    return s_last, counts(ev, steps)

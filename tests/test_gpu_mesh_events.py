@@ -5,7 +5,8 @@ tests/mesh_grad_scenes.py and device against device.
 Forward: on the rays that are not fragile (the walk's own margin, the mesh backward's silenced set: counted, printed, capped) id,
 step, count, path_state and n_steps are EQUAL and t, alpha, T_in and the path within the checker's bounds.  Backward: the upstream of
 the fragile rays is zero, and every gradient is within 4 x the scene's own float32 figure x scale (mesh_event_check.MEASURED_F32,
-measured on the CPU from the reference walk and measured again here).  The walks are mesh_pick_check.walked's, held once per run."""
+measured on the CPU from the reference walk and measured again here).  The walks are mesh_pick_check.walked's, held once per run.
+The upstream here is dense; sparse columns, pages of the backward, windows, views and updated scenes: tests/test_gpu_mesh_events_edges.py."""
 import ctypes as C
 
 import numpy as np

@@ -2,7 +2,9 @@
 tests/mesh_grad_scenes.py, on the walk tests/test_mesh_pick_check.py proves: the lists read back are the walk's arrays, pages
 concatenate, the fragile rays are counted and capped, every seeded fault is named by its comparison, the backward is
 mesh_grad_check's chain below alpha, and the float32 figures that set the GPU's tolerance are measured again.  One test holds the
-built library to the four entry points (it fails before they exist)."""
+built library to the four entry points (it fails before they exist).  The sparse upstreams, pages and windows of
+mesh_event_check.CASES — what exercises the backward's early leave — are the patterns they are named after, each has its own
+float32 figure measured again, and the three faults of that leave are named on the cases the device tests run."""
 import copy
 import ctypes as C
 import functools
@@ -155,7 +157,7 @@ def test_checker_names_seeded_forward_faults(name, fault):
         assert sorted(bad) == sorted(expect)
 
 
-@pytest.mark.parametrize("fault", V.BACKWARD_FAULTS + ("slot_counts_all_steps",))
+@pytest.mark.parametrize("fault", V.CHAIN_FAULTS + ("slot_counts_all_steps",))
 @pytest.mark.parametrize("name", NAMES)
 def test_checker_names_seeded_backward_faults(name, fault):
     s = X.walked(name)
@@ -236,6 +238,116 @@ def test_float32_evaluation_that_sets_the_tolerance(name):
           f"error / scale: {m}; figures {V.MEASURED_F32[name]}")
     for k in V.GROUPS:
         assert V.MEASURED_F32[name][k] / 2 < m[k] <= V.MEASURED_F32[name][k], (k, m[k])
+
+
+def test_sparse_upstreams_are_the_patterns_they_are_named_after():
+    """sparse_upstream() on `mirror`: seeded values of upstream()'s generator, the fragile columns zero, and per pattern the slots the
+    module docstring states — with the stop of `one_mid` falling at every phase of a round of seven."""
+    s = X.walked("mirror")
+    ev = s["ev"]
+    K = V.BACKWARD_K["mirror"]
+    dense, _ = V.upstream(s, ev, K)
+    cnt = np.minimum(V.counts(ev), K)
+    frag = V.fragile(ev)
+    assert np.array_equal(cnt, np.minimum(np.bincount(ev.ray, minlength=ev.n_rays), K)) and frag.sum() == V.MEASURED_FRAGILE["mirror"]
+    assert np.array_equal(V.counts(ev, X.BEHIND) + V.counts(ev, (1, 1)), V.counts(ev))
+    got = {}
+    for pattern in V.SPARSE_PATTERNS:
+        g, n_sil = V.sparse_upstream(s, ev, K, pattern)
+        nz = g != 0
+        assert n_sil == frag.sum() and not nz[:, frag].any() and np.array_equal(g[nz & (dense != 0)], dense[nz & (dense != 0)])
+        assert np.array_equal(g, V.sparse_upstream(s, ev, K, pattern)[0])  # seeded
+        got[pattern] = nz
+        s_last, c = V.stop_of(g, ev)
+        assert np.array_equal(c, V.counts(ev)) and np.array_equal(s_last >= 0, nz.any(0))
+        assert all(nz[s_last[r], r] and not nz[s_last[r] + 1:, r].any() for r in np.nonzero(s_last >= 0)[0][::37])
+    ok = ~frag
+    assert got["head"][0, ok].all() and not got["head"][1:].any()
+    with_events = ok & (cnt > 0)
+    for pattern in ("last", "one_mid"):
+        assert np.array_equal(got[pattern].sum(0), with_events.astype(np.int64))
+    at_last, at_mid = np.argmax(got["last"], 0), np.argmax(got["one_mid"], 0)
+    assert np.array_equal(at_last[with_events], cnt[with_events] - 1) and (at_mid[with_events] < cnt[with_events]).all()
+    assert sorted(set(((at_mid[with_events] + 1) % V.ROUND).tolist())) == list(range(V.ROUND))
+    holes = got["holes"]
+    last_nz = K - 1 - np.argmax(holes[::-1], 0)
+    gaps = [r for r in np.nonzero(holes.any(0))[0] if not holes[:last_nz[r], r].all()]
+    print(f"mirror, holes: {int(holes.any(0).sum())} non-zero columns, {len(gaps)} with a zero slot in front of their last non-zero one; "
+          f"kept {holes.sum() / max(1, (np.arange(K)[:, None] <= last_nz[None, :])[:, holes.any(0)].sum()):.2f} of the slots up to it")
+    assert (last_nz[holes.any(0)] < cnt[holes.any(0)]).all() and len(gaps) > 500
+    for pattern in ("one_per_tile", "one_tile"):
+        m, longest = V.wave_mask(s, ev, pattern)
+        assert m[longest] and not frag[longest] and np.array_equal(got[pattern].any(0), m) and got[pattern][:, m].all()
+        w, h = s["p"].width, s["p"].height
+        yy, xx = np.divmod(np.nonzero(m)[0], w)
+        per_tile = np.bincount((yy // 8) * (-(-w // 8)) + xx // 8, minlength=(-(-w // 8)) * (-(-h // 8)))
+        if pattern == "one_per_tile":  # (a cut tile at the frame's edge may not hold the lane)
+            assert per_tile.max() == 1 and per_tile.sum() >= (w // 8) * (h // 8)
+        else:
+            assert (per_tile > 0).sum() == 1
+
+
+STOP_FAULT_CASES = {"leaves_at_first_zero_slot": "mirror/holes", "stop_ignores_first": "glass/last/first_32",
+                    "stop_counts_all_steps": "mirror/last/behind"}
+
+
+@pytest.mark.parametrize("fault", V.STOP_FAULTS)
+def test_checker_names_the_faults_of_the_early_leave(fault):
+    """A lane of the device's backward that leaves its walk at a wrong event number drops the events behind the round it leaves in.
+    Each such fault, modelled at that granularity (only the events that are certainly lost are dropped), is named in pos and opacity
+    on a case the device tests run, at that case's own tolerance — and not by one ray: at least 50 events on at least 20 rays."""
+    key = STOP_FAULT_CASES[fault]
+    c = V.case(key)
+    ev, tol = c["ev"], V.tol_of_case(key)
+    g_bad = V.event_upstream(c["g"], ev, c["first"], c["steps"], fault=fault)
+    dropped = (c["g_ev"] != 0) & (g_bad == 0)
+    assert np.array_equal(g_bad[~dropped], c["g_ev"][~dropped])
+    print(f"{fault} on {key}: {int(dropped.sum())} of {int((c['g_ev'] != 0).sum())} events with an upstream value dropped, on "
+          f"{len(np.unique(ev.ray[dropped]))} rays")
+    assert dropped.sum() >= 50 and len(np.unique(ev.ray[dropped])) >= 20
+    got, _ = V.evaluate_backward(c["s"]["parts"], ev, g_bad)
+    bad = V.compare_backward(got, c["want"], c["scale"], tol)
+    print(f"{fault} on {key}: {({k: len(v) for k, v in bad.items()})} values named")
+    assert "pos" in bad and "opacity" in bad, (fault, list(bad))
+    assert not V.compare_backward(c["want"], c["want"], c["scale"], 0.0)
+    # without the fault's precondition nothing is dropped: the dense upstream of the whole ray, first = 0, all steps
+    dense, _ = V.upstream(c["s"], ev, V.BACKWARD_K[c["s"]["name"]])
+    assert np.array_equal(V.event_upstream(dense, ev, fault=fault), V.event_upstream(dense, ev))
+
+
+@pytest.mark.parametrize("key", sorted(V.CASES))
+def test_float32_figure_of_every_case_is_measured_again(key):
+    """Every upstream the device tests use beside the dense one has its own figure (a sparse upstream has a smaller scale: the dense
+    figure is not borrowed): measured again here and held in (figure / 2, figure]; the fragile rays are the walk's own, whatever
+    the upstream."""
+    assert sorted(V.CASES) == sorted(V.MEASURED_F32_CASES)
+    name, pattern, K, first, steps = V.CASES[key]
+    c = V.case(key)
+    s, ev, g = c["s"], c["ev"], c["g"]
+    frag = V.fragile(ev)
+    if name == V.UPDATED:
+        assert c["n_silenced"] == frag.sum() <= G.MAX_SILENCED * s["n_traced"]
+    else:
+        assert c["n_silenced"] == frag.sum() == V.MEASURED_FRAGILE[name] <= G.MAX_SILENCED * s["n_traced"]
+    assert g.shape == (K, ev.n_rays) and not g[:, frag].any() and c["first"] == first and c["steps"] == steps
+    if pattern in V.SPARSE_PATTERNS + ("window",):
+        assert K == V.BACKWARD_K[name]
+    if name == V.UPDATED:
+        assert K == V.FORWARD_K["mirror"]
+    m = V.measure_f32(s["parts"], ev, c["g_ev"])
+    fig = V.MEASURED_F32_CASES[key]
+    print(f"{key}: {int((g != 0).any(0).sum())} non-zero columns, {int((c['g_ev'] != 0).sum())} events with an upstream value; float32 "
+          f"evaluation, error / scale: {({k: f'{v:.3e}' for k, v in m.items()})}; figures {fig}")
+    assert (c["g_ev"] != 0).sum() >= 50
+    for k in V.GROUPS:
+        assert fig[k] / 2 < m[k] <= fig[k], (k, m[k])
+        assert V.tol_of_case(key)[k] == 4 * max(fig[k], 2.0 ** -23)
+    if name == V.UPDATED:  # a small step away from `mirror`: its figures are of the size of mirror's own (a tolerance cannot grow unseen)
+        assert all(V.MEASURED_F32["mirror"][k] / 4 < fig[k] < 4 * V.MEASURED_F32["mirror"][k] for k in V.GROUPS)
+        wfig = max(MS.measure_f32(s["parts"], ev, MS.ray_weights(name, ev)[0]).values())  # and its lists' alpha and T_in
+        print(f"{name}: float32 statistics, error / scale {wfig:.3e}; figure {V.MEASURED_F32_WEIGHT[name]}, mirror's {MS.MEASURED_F32['mirror']}")
+        assert V.MEASURED_F32_WEIGHT[name] / 2 < wfig <= V.MEASURED_F32_WEIGHT[name] < 4 * MS.MEASURED_F32["mirror"]
+        assert len(ev.ray) > s["n_traced"] and int(np.bincount(ev.ray, minlength=ev.n_rays).max()) <= K
 
 
 def test_off_centre_glass_bends_every_ray_and_names_the_camera_ray():
