@@ -150,6 +150,16 @@ class SegmentOut(C.Structure):
     _fields_ = [("radiance", C.c_void_p), ("T_out", C.c_void_p), ("depth", C.c_void_p), ("count", C.c_void_p)]
 
 
+class DepthOut(C.Structure):
+    """grt_depth_out (include/grt.h): device pointers of dist / dist2 / T_out / count [N], each may be NULL, not all."""
+    _fields_ = [("dist", C.c_void_p), ("dist2", C.c_void_p), ("T_out", C.c_void_p), ("count", C.c_void_p)]
+
+
+class DepthUpstream(C.Structure):
+    """grt_depth_upstream (include/grt.h): device pointers of dloss/ddist, dloss/ddist2 and dloss/dT_out [N], each may be NULL, not all."""
+    _fields_ = [("dist", C.c_void_p), ("dist2", C.c_void_p), ("T_out", C.c_void_p)]
+
+
 class FeatureGrads(C.Structure):
     """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
@@ -179,6 +189,9 @@ MESH_EVENT_FIELDS = ("id", "t", "alpha", "step", "count", "T_in")
 MESH_PATH_FIELDS = ("path_rays", "path_t_far", "path_state", "n_steps")
 STEP_LAST, STEP_GAUSSIAN, STEP_TERMINATE = 0, 1, 3  # GRT_STEP_*: the states in path_state (PICK_NONE: an unused path slot)
 SEGMENT_OUTPUTS = ("radiance", "T_out", "depth", "count")
+DEPTH_OUTPUTS = ("dist", "dist2", "T_out", "count")
+DEPTH_KINDS = {"key": 0, "peak": 1}  # GRT_DEPTH_KEY, GRT_DEPTH_PEAK
+DEPTH_GROUPS = ("pos", "scale", "quat", "opacity")
 
 
 class Mesh(C.Structure):
@@ -218,6 +231,7 @@ EXPORTS = [
     "grt_ray_picks_mesh_frame", "grt_ray_picks_mesh_rays", "grt_ray_events_mesh_frame", "grt_ray_events_mesh_rays",
     "grt_backward_events_mesh_frame", "grt_backward_events_mesh_rays",
     "grt_trace_segments_frame", "grt_trace_segments_rays", "grt_backward_segments_frame", "grt_backward_segments_rays",
+    "grt_ray_depth_frame", "grt_ray_depth_rays", "grt_backward_depth_frame", "grt_backward_depth_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_render_features_mesh_frame", "grt_render_features_mesh_rays",
     "grt_backward_features_mesh_frame", "grt_backward_features_mesh_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
@@ -297,6 +311,10 @@ def lib():
         L.grt_trace_segments_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(Segments), C.POINTER(SegmentOut), vp]
         L.grt_backward_segments_frame.argtypes = [vp, C.POINTER(Params), C.POINTER(Segments), vp, vp, C.POINTER(GaussianGrads), u32, u32, u32, u32, vp]
         L.grt_backward_segments_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.POINTER(Segments), vp, vp, C.POINTER(GaussianGrads), vp]
+        L.grt_ray_depth_frame.argtypes = [vp, C.POINTER(Params), C.c_int, C.POINTER(DepthOut), u32, u32, u32, u32, vp]
+        L.grt_ray_depth_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.c_int, C.POINTER(DepthOut), vp]
+        L.grt_backward_depth_frame.argtypes = [vp, C.POINTER(Params), C.c_int, C.POINTER(DepthUpstream), C.POINTER(BackwardOut), u32, u32, u32, u32, vp]
+        L.grt_backward_depth_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.c_int, C.POINTER(DepthUpstream), C.POINTER(BackwardOut), vp]
         L.grt_render_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, vp]
         L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
         L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
@@ -1174,6 +1192,93 @@ class Tracer:
             self._check(lib().grt_backward_segments_frame(self._h, C.byref(params), C.byref(seg), g_R.data_ptr(),
                                                           g_T.data_ptr() if g_T is not None else None, C.byref(ptrs), x0, y0, x1, y1,
                                                           self._stream()))
+        return into
+
+    def _depth_inputs(self, what, params, rays, window, kind):
+        """rays [n][6] (or None) as a contiguous float32 tensor on the tracer's GPU, the shape of one output plane, the window, the
+        device and the kind's number."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        if kind not in DEPTH_KINDS:
+            raise GrtError(f"{what}: kind must be one of {tuple(DEPTH_KINDS)}, not {kind!r}")
+        if rays is not None:
+            if window is not None:
+                raise GrtError(f"{what}: rays and window exclude each other")
+            if rays.dim() != 2 or rays.shape[1] != 6:
+                raise GrtError(f"{what}: rays must have shape [n][6], not {tuple(rays.shape)}")
+            rays = rays.detach().to(dev, t.float32).contiguous()
+            shape = (rays.shape[0],)
+        else:
+            shape = (params.height, params.width)
+        return rays, shape, (window if window else (0, 0, params.width, params.height)), dev, DEPTH_KINDS[kind]
+
+    def ray_depth(self, params, rays=None, window=None, kind="peak", outputs=DEPTH_OUTPUTS):
+        """grt_ray_depth_frame / grt_ray_depth_rays (rays [n][6] given): the distance moments of every whole ray -> dict of torch
+        tensors [n] or [h][w] on the tracer's GPU: 'dist' (sum w_i tau_i), 'dist2' (sum w_i tau_i^2), 'T_out' (prod (1 - alpha_i)) and
+        'count' (uint32); include/grt.h.  kind "key": tau_i is the event's key distance (the aux depth's); "peak": the distance of the
+        particle's maximum response along the ray, which is differentiable (backward_depth).  tau is in units of |d|, not clamped to
+        the range and may be negative; dist / (1 - T_out) is the mean.  An untraced ray and a pixel outside a window hold 0, 0, 1, 0.
+        Bitwise reproducible."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, kind = self._depth_inputs("ray_depth", params, rays, window, kind)
+        outputs = tuple(outputs)
+        if not outputs or any(k not in DEPTH_OUTPUTS for k in outputs):
+            raise GrtError(f"ray_depth: outputs must be a non-empty subset of {DEPTH_OUTPUTS}, not {outputs}")
+        make = {"dist": lambda: t.zeros(shape, dtype=t.float32, device=dev), "dist2": lambda: t.zeros(shape, dtype=t.float32, device=dev),
+                "T_out": lambda: t.ones(shape, dtype=t.float32, device=dev),
+                "count": lambda: t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32)}
+        out = {k: make[k]() for k in DEPTH_OUTPUTS if k in outputs}
+        if not shape[0] or not shape[-1]:  # (no ray: nothing to write.  An empty scene goes to the library: its refusals hold)
+            return out
+        ptrs = DepthOut(*(out[k].data_ptr() if k in out else None for k in DEPTH_OUTPUTS))
+        if rays is not None:
+            self._check(lib().grt_ray_depth_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], kind, C.byref(ptrs), self._stream()))
+        else:
+            self._check(lib().grt_ray_depth_frame(self._h, C.byref(params), kind, C.byref(ptrs), x0, y0, x1, y1, self._stream()))
+        return out
+
+    def backward_depth(self, params, grad_dist=None, grad_dist2=None, grad_T_out=None, rays=None, window=None, kind="peak", into=None,
+                       groups=None, ray_grads=False):
+        """grt_backward_depth_frame / grt_backward_depth_rays: grad_dist, grad_dist2, grad_T_out [n] or [h][w] (each may be None, not
+        all) hold dloss/ddist, dloss/ddist2 and dloss/dT_out of what ray_depth computed (same params, rays / window, kind) -> dict of
+        torch tensors pos, scale, quat, opacity: the gradients with respect to the uploaded Gaussians, allocated zeroed for `groups`
+        (default: all four) or ACCUMULATED into the tensors of `into`.  ray_grads: the dict also holds "rays" [n][6] or [h][w][6]
+        (dloss/do, dloss/dd as the kernel holds d: no projection), WRITTEN and bitwise reproducible; groups=[] with ray_grads is the
+        rays-only call (no atomics, no gradient buffer).  A ray whose three upstream values are exactly 0 is not traced; include/grt.h."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, kind = self._depth_inputs("backward_depth", params, rays, window, kind)
+        ups = []
+        for name, g in (("grad_dist", grad_dist), ("grad_dist2", grad_dist2), ("grad_T_out", grad_T_out)):
+            if g is not None and (not t.is_tensor(g) or tuple(g.shape) != shape):
+                raise GrtError(f"backward_depth: {name} must be a tensor of shape {list(shape)}")
+            ups.append(g.detach().to(dev, t.float32).contiguous() if g is not None else None)
+        if all(g is None for g in ups):
+            raise GrtError("backward_depth: no upstream (grad_dist, grad_dist2 and grad_T_out are all None)")
+        if any(k not in DEPTH_GROUPS for k in (groups or ())):  # (an 'sh' tensor in `into` is handed on and left untouched)
+            raise GrtError(f"backward_depth: the gradient groups are {DEPTH_GROUPS} (the depth has no colour)")
+        if groups is None and into is None:
+            groups = DEPTH_GROUPS
+        if ray_grads:
+            into, out, hold = self._ex_buffers(into, groups, dev, shape + (6,))
+        else:
+            if (into is not None and not into) or (into is None and not len(groups)):
+                raise GrtError("backward_depth: no gradient group asked for")
+            into, hold = self._grad_buffers(into, groups, dev)
+            out = BackwardOut(C.pointer(hold), None)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        # (no ray: nothing to write.  An empty scene has no gradient array to point at — its tensors hold no element —, so only a call
+        # with the rays' output goes to the library, which WRITES that output's zeros)
+        if not shape[0] or not shape[-1] or (not n and not ray_grads):
+            return into
+        if not n:
+            out = BackwardOut(None, into["rays"].data_ptr())
+        up = DepthUpstream(*(g.data_ptr() if g is not None else None for g in ups))
+        if rays is not None:
+            self._check(lib().grt_backward_depth_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], kind, C.byref(up), C.byref(out),
+                                                      self._stream()))
+        else:
+            self._check(lib().grt_backward_depth_frame(self._h, C.byref(params), kind, C.byref(up), C.byref(out), x0, y0, x1, y1,
+                                                       self._stream()))
         return into
 
     def _feature_inputs(self, what, params, feat, rays, window):

@@ -37,6 +37,12 @@ on the events' alpha and distances is differentiable with respect to the four ge
 
 traces ONE segment of every ray with a range and an entering transmittance per ray: the plain radiance and the
 transmittance behind it, differentiable with respect to the five tensors and to T_in — a depth-buffer composite or a bounce loop in torch.
+
+    dist, dist2, T_out, count = grt_torch.ray_depth(tracer, params, geometry=(pos, scale, quat, opacity), camera=(eye, U, V, W))
+
+gives every whole ray's distance moments: dist / (1 - T_out) is the mean depth at the particles' maximum response,
+differentiable with respect to the four geometry tensors, to `rays` and to the camera — a LiDAR or monocular-depth loss, a variance
+regulariser, pose refinement from a depth map.
 """
 import numpy as np
 import torch
@@ -469,3 +475,90 @@ def trace_segments(tracer, params, rays, t_near=None, t_far=None, T_in=None, gau
             raise ValueError(f"grt_torch.trace_segments: gaussians tensor '{name}' must have shape {shape} (the tracer's last upload), "
                              f"not {tuple(t.shape)}")
     return _TraceSegments.apply(*gs, T_in, rays, t_near, t_far, window, tracer, params)
+
+
+class _RayDepth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, scale, quat, opacity, rays, cam_rays, window, kind, tracer, params):
+        # pos .. opacity: the tensors of the tracer's last upload, or None: only the carriers of the gradients; rays: a ray buffer
+        # [n][6], or None for the camera frame of `params`; cam_rays: camera_rays() of that camera, the carrier of the per-pixel gradient
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.params, ctx.window, ctx.kind = tracer, params, window, kind
+        ctx.rays = rays.detach().to(f"cuda:{tracer.device}", torch.float32).contiguous() if rays is not None else None
+        ctx.rays_like = (rays.device, rays.dtype) if rays is not None else None
+        ctx.cam_like = (cam_rays.device, cam_rays.dtype) if cam_rays is not None else None
+        ctx.like = tuple((t.device, t.dtype) if t is not None else None for t in (pos, scale, quat, opacity))
+        out = tracer.ray_depth(params, rays=ctx.rays, window=window, kind=kind)
+        ctx.mark_non_differentiable(out["count"])
+        return out["dist"], out["dist2"], out["T_out"], out["count"]
+
+    @staticmethod
+    def backward(ctx, g_D, g_D2, g_T, g_count):
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("pos", "scale", "quat", "opacity")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:4]) if want]
+        want_rays, want_cam = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        ups = [g.to(f"cuda:{tr.device}", torch.float32).contiguous() if g is not None else None for g in (g_D, g_D2, g_T)]
+        if (not groups and not want_rays and not want_cam) or all(g is None for g in ups):
+            return (None,) * 10
+        g = tr.backward_depth(ctx.params, *ups, rays=ctx.rays, window=ctx.window, kind=ctx.kind, groups=groups,
+                              ray_grads=bool(want_rays or want_cam))  # (no group wanted: the rays-only kernel)
+        out = tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like))
+        g_rays = g["rays"].to(*ctx.rays_like) if want_rays else None
+        g_cam = g["rays"].to(*ctx.cam_like) if want_cam else None
+        return out + (g_rays, g_cam, None, None, None, None)
+
+
+def ray_depth(tracer, params, geometry=None, rays=None, camera=None, kind="peak", window=None):
+    """(dist, dist2, T_out, count) of every whole ray (Tracer.ray_depth; include/grt.h: grt_ray_depth_frame / _rays):
+    dist = sum w_i tau_i, dist2 = sum w_i tau_i^2, T_out = prod (1 - alpha_i) and the event count, with tau_i the distance of the
+    particle's maximum response along the ray (kind "peak") or the event's key distance (kind "key": the aux depth, whose distances
+    are data).  tau is in units of |d|; dist / (1 - T_out) is the mean depth.  rays [n][6], or None for the camera frame of `params`
+    (its `window`), or of camera=(eye, U, V, W) written into a copy of `params`.
+    Without `geometry`, and with neither rays nor camera requiring grad, it is the plain call under torch.no_grad().  dist, dist2 and
+    T_out are differentiable with respect to geometry=(pos, scale, quat, opacity) through the kernel (grt_backward_depth_*), with
+    respect to `rays` when it requires grad ([n][6]: dloss/do, dloss/dd), and with respect to the four tensors of `camera` through
+    camera_rays() in torch and the per-pixel rays output, as render() does.  count carries no gradient.
+    It traces the scene the tracer HOLDS and uploads nothing, like trace_segments: the `geometry` tensors only carry the gradient —
+    they must be the tensors of the tracer's last upload, their shapes are checked against the tracer's particle count and their
+    values are not read.  The backward raises GrtError when the tracer has received another upload since the forward.  A tracer with
+    meshes: ValueError (the ray depth is the Gaussian-only call)."""
+    if tracer.has_meshes:
+        raise ValueError("grt_torch.ray_depth: meshes are set on this tracer; the ray depth is the Gaussian-only call")
+    if kind not in grt.DEPTH_KINDS:
+        raise ValueError(f"grt_torch.ray_depth: kind must be one of {tuple(grt.DEPTH_KINDS)}, not {kind!r}")
+    if rays is not None and (not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] != 6):
+        raise ValueError(f"grt_torch.ray_depth: rays must be a tensor of shape [n][6], not {tuple(rays.shape) if torch.is_tensor(rays) else type(rays)}")
+    cam_rays = None
+    if camera is not None:
+        if rays is not None:
+            raise ValueError("grt_torch.ray_depth: rays and camera exclude each other")
+        eye, U, V, W = camera
+        params = type(params).from_buffer_copy(params)
+        for name, t in (("eye", eye), ("U", U), ("V", V), ("W", W)):
+            v = t.detach().to("cpu", torch.float32).reshape(3)
+            for k in range(3):
+                getattr(params, name)[k] = float(v[k])
+        if any(t.requires_grad for t in camera):
+            cam_rays, _ = camera_rays(eye, U, V, W, params.width, params.height, bool(params.mode_fisheye))
+    gs = (None,) * 4
+    if geometry is not None:
+        gs = tuple(geometry)
+        scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene)
+        n = scene.n_particles
+        want = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,)}
+        if len(gs) != 4 or any(not torch.is_tensor(t) for t in gs):
+            raise ValueError("grt_torch.ray_depth: geometry must be four tensors (pos, scale, quat, opacity)")
+        for (name, shape), t in zip(want.items(), gs):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"grt_torch.ray_depth: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
+                                 f"not {tuple(t.shape)}")
+    if geometry is None and cam_rays is None and not (rays is not None and rays.requires_grad):
+        with torch.no_grad():
+            out = tracer.ray_depth(params, rays=rays, window=window, kind=kind)
+        return tuple(out[k] for k in grt.DEPTH_OUTPUTS)
+    return _RayDepth.apply(*gs, rays, cam_rays, window, kind, tracer, params)

@@ -455,7 +455,7 @@ GRT_API int grt_render_rays_aux(grt_ctx* ctx, const grt_params* p, const float* 
  *     d/dmu = A^T g_p,   d/ds_k = -g_p,k (R^T v)_k / s_k^2,   d/dR_jk = v_j g_p,k / s_k -> q through mat3_cast.
  * Gradients are with respect to the ACTIVATED attributes of grt_gaussians; the chain through exp / sigmoid / normalise is the
  * caller's.  Gradients with respect to rays / camera come from grt_backward_ex below; upstream gradients of depth / count are
- * not computed.
+ * not computed (a distance with gradients: grt_ray_depth_* / grt_backward_depth_* below).
  *   d_rgbf, d_alpha          what the forward call wrote for the same parameters and window (grt_render_aux: d_rgbf and aux.alpha);
  *                            required.  (The kernel re-derives rad and T_end with a sweep of its own: DESIGN.md 5.8.)
  *   d_grad_rgbf, d_grad_alpha  upstream gradients, laid out like d_rgbf / alpha; d_grad_alpha may be NULL (= 0).
@@ -964,7 +964,8 @@ GRT_API int grt_backward_events_mesh_rays(grt_ctx* ctx, const grt_params* p, con
  * no forward outputs: its first sweep recomputes R and T_out.  A ray whose four upstream values are exactly 0 is not traced; nothing goes
  * into opacity or geometry where the 0.99 clamp binds.  Through the context's gradient buffer and its flush exactly as grt_backward.
  * Float atomics: not bitwise reproducible; GRT_OPT_BWD_PLAIN_ATOMICS = 1 makes every lane issue its own (testing).  The distances
- * (t_near, t_far, t_i in depth) and the event set are DATA: no gradients through them, through the rays, or through depth / count.  With
+ * (t_near, t_far, t_i in depth) and the event set are DATA: no gradients through them, through the rays, or through depth / count
+ * (whole rays: grt_ray_depth_* below).  With
  * the event set fixed R and T_out are linear in T_in, so dloss/dT_in = (g_R . R + g_T T_out) / T_in is the caller's to form.
  * Both: asynchronous on `stream` like grt_render; grt_last_kernel_ms reports the call's device time; a view computes its scene's
  * result.  With n = 0 rays or an empty window the calls return GRT_OK and write nothing; with no particles or an empty tree the forward
@@ -994,6 +995,68 @@ GRT_API int grt_backward_segments_rays(grt_ctx* ctx, const grt_params* p, const 
 GRT_API int grt_backward_segments_frame(grt_ctx* ctx, const grt_params* p, const grt_segments* seg, const float* d_grad_radiance,
                                         const float* d_grad_T_out /* may be NULL */, const grt_gaussian_grads* out, uint32_t x0, uint32_t y0,
                                         uint32_t x1, uint32_t y1, void* stream);
+/* ---- differentiable ray depth: key or peak distance, two moments, gradients ----
+ * grt_aux_out::depth and grt_segment_out::depth are sums over the proxies' entry / exit face distances and carry no gradient.  These
+ * calls give a WHOLE ray's distance moments with gradients to the Gaussians and to the ray, for Gaussian-only scenes (depth-supervised
+ * fitting, depth-variance regularisers, pose refinement from a depth map).
+ * FORWARD.  For a ray (o, d) the events i are exactly those grt_trace_segments_* composites with its defaults (p->t_min, p->t_max,
+ * T = 1; p->max_bounces is not looked at).  With w_i = T_i alpha_i and T_out = prod_i (1 - alpha_i):
+ *     dist  [N]  sum_i w_i tau_i         accumulated as the aux depth is: (T alpha) tau added before T is updated
+ *     dist2 [N]  sum_i w_i tau_i^2       ((T alpha) tau) tau, likewise
+ *     T_out [N]  the transmittance behind the ray,   count [N]  composited events
+ *     GRT_DEPTH_KEY  (0): tau_i = the event's key distance (the t_i of grt_aux_out::depth)
+ *     GRT_DEPTH_PEAK (1): tau_i = d_val,i = -(o_g.d_g) / max(1e-6, d_g.d_g),  o_g = A (o - mu),  d_g = A d,  A = diag(1/s) R^T: the
+ *                         distance of the particle's maximum response along the ray (computeResponse, shaders/tracer.cuh:187-214)
+ * tau is in units of |d| and is NOT normalised: dist / (1 - T_out) is the mean distance, dist2 / (1 - T_out) - mean^2 its variance.
+ * Under PEAK the entry and the exit event of a particle carry the same tau.  tau is NOT clamped to the ray's range and MAY BE NEGATIVE
+ * (a particle whose centre lies behind the origin but whose proxy the ray still meets).  With KEY, dist, count and 1 - T_out equal
+ * grt_render_rays_aux's depth, count and alpha bit for bit (at max_bounces > 0).  An untraced ray (fisheye r > 1, |d| <= 0.1, a NaN
+ * direction, an empty tree) writes 0, 0, T_out = 1, 0.  Every element of the buffer or of the window is WRITTEN once per requested
+ * array; pixels outside the window are untouched.  No atomic, no wave operation, no buffer of the context: the call is BITWISE
+ * reproducible and windows tile a frame bit for bit.
+ * BACKWARD.  Upstreams g_D = dloss/ddist, g_D2 = dloss/ddist2, g_T = dloss/dT_out, [N] each, each may be NULL (zero), not all.  Every
+ * discrete decision is held fixed as in grt_backward.  With f_i = g_D tau_i + g_D2 tau_i^2 and S_i = sum_{j>i} w_j f_j:
+ *     dloss/dalpha_i = T_i f_i - (S_i + g_T T_out) / (1 - alpha_i)     down to pos, scale, quat, opacity as in grt_backward (zero
+ *                                                                      where the 0.99 clamp binds)
+ *     dloss/dtau_i   = w_i (g_D + 2 g_D2 tau_i)                        PEAK only; NOT gated by the 0.99 clamp (tau does not pass
+ *                                                                      through it).  Under KEY the distances are data.
+ * Below tau, with q = max(1e-6, d_g.d_g), a = -d_g / q, p_g = -(o_g + tau d_g) and b = (p_g - tau d_g) / q:
+ *     dtau/dmu = A^T d_g / q,   dtau/do = -A^T d_g / q,   dtau/dd = A^T b,   dtau/ds_k = -(a_k o_g,k + b_k d_g,k) / s_k,
+ *     dtau/dR_jk = (a_k (o - mu)_j + b_k d_j) / s_k -> q through mat3_cast.
+ * Where max(1e-6, .) binds the denominator is a constant (grt_backward_ex's convention): b = -o_g / q.
+ *   out->gaussians   ADDED to, by original id: pos, scale, quat, opacity.  A non-NULL sh is left untouched and is not a request.
+ *   out->rays        [N][6], WRITTEN: dloss/do = -sum_i m_i + sum_i gtau_i dtau_i/do,  dloss/dd = -sum_i d_val,i m_i + sum_i gtau_i
+ *                    dtau_i/dd  (m_i as in grt_backward_ex).  RAW partials with respect to d as the kernel holds it: there is no SH
+ *                    term and so no projection; for camera frames the chain to U, V, W is the caller's.  Exact zeros for an untraced
+ *                    ray and for a ray whose three upstream values are exactly 0 (such a ray is not traced).  No atomic in its path:
+ *                    BITWISE reproducible, with and without the Gaussian output, merged or plain atomics.
+ * The Gaussians' gradients go through the context's gradient buffer and its flush exactly as grt_backward's (float atomics, not
+ * bitwise reproducible; GRT_OPT_BWD_PLAIN_ATOMICS = 1 as there); a call with out->gaussians NULL allocates no gradient buffer.
+ * Both: asynchronous on `stream`; grt_last_kernel_ms reports the call's device time; a view computes its scene's result.  With n = 0
+ * rays or an empty window the calls return GRT_OK and write nothing.
+ * Refused with GRT_ERR_INVALID (text in grt_last_error with the entry point's name in front; the context stays usable): everything
+ * grt_backward refuses, meshes set, an unknown kind, no output (forward: out NULL or all four arrays NULL; backward: out NULL, or rays
+ * NULL and no pos / scale / quat / opacity array), no upstream (up NULL or all three NULL). */
+enum { GRT_DEPTH_KEY = 0, GRT_DEPTH_PEAK = 1 };
+typedef struct grt_depth_out {      /* device pointers, each may be NULL, not all */
+    float* dist;                    /* [N]  sum_i w_i tau_i */
+    float* dist2;                   /* [N]  sum_i w_i tau_i^2 */
+    float* T_out;                   /* [N]  prod_i (1 - alpha_i) */
+    uint32_t* count;                /* [N]  composited events */
+} grt_depth_out;
+typedef struct grt_depth_upstream { /* device pointers, [N] float32 each; each may be NULL (zero), not all */
+    const float* dist;
+    const float* dist2;
+    const float* T_out;
+} grt_depth_upstream;
+GRT_API int grt_ray_depth_frame(grt_ctx* ctx, const grt_params* p, int kind, const grt_depth_out* out, uint32_t x0, uint32_t y0,
+                                uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_ray_depth_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, int kind, const grt_depth_out* out,
+                               void* stream);
+GRT_API int grt_backward_depth_frame(grt_ctx* ctx, const grt_params* p, int kind, const grt_depth_upstream* up,
+                                     const grt_backward_out* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_depth_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, int kind,
+                                    const grt_depth_upstream* up, const grt_backward_out* out, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
