@@ -179,6 +179,7 @@ int grt_set_option(grt_ctx* c, int option, int value)
     else if (option == GRT_OPT_TILE_PRIO_DIV) { c->opt_tile_prio = std::max(0, value); }
     else if (option == GRT_OPT_BWD_PLAIN_ATOMICS) { c->opt_bwd_plain = value ? 1 : 0; }
     else if (option == GRT_OPT_REFIT_MAX_AREA_PCT) { NOT_A_VIEW(c, "GRT_OPT_REFIT_MAX_AREA_PCT"); c->opt_refit_max_area_pct = std::max(0, value); }
+    else if (option == GRT_OPT_ALPHA_CULL) { c->opt_alpha_cull = value ? 1 : 0; }
     else if (option == GRT_OPT_TILE_RESERVE) { c->opt_tile_reserve = std::min(63, std::max(-1, value)); }
     else if (option == GRT_OPT_LEAF_MAX) {
         if (value < 1 || value > (int)kLeafMaxPrims) { c->err = "GRT_OPT_LEAF_MAX must be 1..8"; return GRT_ERR_INVALID; }
@@ -301,6 +302,7 @@ int grt_get_memory_info(const grt_ctx* c, grt_memory_info* o)
     b += nf * (48 + 12) + nv * 12 + sc->mbvh.cap_nodes * 64 + sc->mbvh.cap_order * 4 + (sc->mbvh.wnodes && nf > 1 ? (nf - 1) * 128 : 0) +
          (sc->mbvh.level && nf > 1 ? (nf - 1) * 4 : 0);
     o->scene_bytes = b;
+    o->alpha_cull_bytes = sc->gbvh.pbox_a ? m * 32 : 0;                       // (beside scene_bytes, whose sum stays the one of the arrays above)
     uint64_t v = (uint64_t)c->cap_erec * 16 + (uint64_t)c->cap_erec_wide * 64;
     v += (uint64_t)c->ovf_chunks * kTileOvfChunkBytes;
     v += (uint64_t)c->cost_cap * 12;

@@ -1187,19 +1187,25 @@ __global__ void k_qwiden(const float4* __restrict__ nodes, int m, float4* __rest
     }
 }
 
+// pbox: (lo.xyz, 0)(hi.xyz, hi.w); pbox_a: the same box with the alpha radius, which the sorted boxes carry in lo.w (DevBvh, grt_internal.h)
 __global__ void k_pbox(const float4* __restrict__ lb_lo, const float4* __restrict__ lb_hi, uint32_t m,
-                       float4* __restrict__ pbox)
+                       float4* __restrict__ pbox, float4* __restrict__ pbox_a)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
-    pbox[(size_t)j * 2] = lb_lo[j];
-    pbox[(size_t)j * 2 + 1] = lb_hi[j];
+    const float4 l = lb_lo[j], h = lb_hi[j];
+    const float4 l0 = make_float4(l.x, l.y, l.z, 0.0f);
+    pbox[(size_t)j * 2] = l0;
+    pbox[(size_t)j * 2 + 1] = h;
+    pbox_a[(size_t)j * 2] = l0;
+    pbox_a[(size_t)j * 2 + 1] = make_float4(h.x, h.y, h.z, l.w);
 }
 
 void free_bvh(DevBvh* b)
 {
     if (b->qnodes) (void)hipFree(b->qnodes);
     if (b->pbox) (void)hipFree(b->pbox);
+    if (b->pbox_a) (void)hipFree(b->pbox_a);
     if (b->level) (void)hipFree(b->level);
     if (b->wnodes) (void)hipFree(b->wnodes);
     if (b->nodes) (void)hipFree(b->nodes);
@@ -1313,7 +1319,7 @@ int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh,
     const int B = 256;
     const uint32_t grid = m > 1 ? (m - 1 + B - 1) / B : 1u;
     if (m == 0) return GRT_OK;
-    if (bvh->pbox) hipLaunchKernelGGL(k_pbox, dim3((m + B - 1) / B), dim3(B), 0, stream, d_lb_lo, d_lb_hi, m, bvh->pbox);
+    if (bvh->pbox && bvh->pbox_a) hipLaunchKernelGGL(k_pbox, dim3((m + B - 1) / B), dim3(B), 0, stream, d_lb_lo, d_lb_hi, m, bvh->pbox, bvh->pbox_a);
     if (bvh->root_ref & kLeafBit) { HIPCHK(hipGetLastError()); return GRT_OK; } // one leaf range: no node arrays
     if (!bvh->nodes || !bvh->wnodes) {
         if (err) *err = "refit_sorted_lbvh: the tree has no node arrays";
@@ -1432,8 +1438,9 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
     }
     if (out->qnodes) (void)hipFree(out->qnodes);
     if (out->pbox) (void)hipFree(out->pbox);
+    if (out->pbox_a) (void)hipFree(out->pbox_a);
     if (out->level) (void)hipFree(out->level);
-    out->qnodes = out->pbox = nullptr;
+    out->qnodes = out->pbox = out->pbox_a = nullptr;
     out->level = nullptr;
     if (m) {
         HIPCHK(hipMalloc(&d_lblo, sizeof(float4) * m));
@@ -1442,7 +1449,8 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
                            d_lbhi);
         if (want_quad) {
             HIPCHK(hipMalloc(&out->pbox, sizeof(float4) * 2 * (size_t)m + 256));
-            hipLaunchKernelGGL(k_pbox, dim3((m + B - 1) / B), dim3(B), 0, stream, d_lblo, d_lbhi, m, out->pbox);
+            HIPCHK(hipMalloc(&out->pbox_a, sizeof(float4) * 2 * (size_t)m + 256));
+            hipLaunchKernelGGL(k_pbox, dim3((m + B - 1) / B), dim3(B), 0, stream, d_lblo, d_lbhi, m, out->pbox, out->pbox_a);
         }
     }
     if (m <= leaf_max) { // empty, or the whole scene is one leaf range: no node arrays (drop stale ones of an earlier build)

@@ -818,6 +818,18 @@ static int tile_tuning(grt_ctx* c, RenderArgs& a, hipStream_t s, bool tile_kerne
     }
     return GRT_OK;
 }
+// 10b. GRT_OPT_ALPHA_CULL: the launches whose pre-test reads the alpha sphere (cc_a of the wide eye records: the uncounted camera-ray
+// kernel with or without the mesh walk, SH and pieces, its aux instantiation, the quad kernel — all of them the PRIMARY stage of a frame
+// on the tile kernel) cull their leaf ranges with the alpha radius.  The stages behind it (bundles, single rays; they may start from a
+// copy of this argument block) pre-test on the circumsphere and take aux.pbox_bundles; counted frames run the full event stream and keep
+// gbvh.pbox, as a frame does whose alpha_min lies below the scene's (alpha_sphere_ok: its cc_a is the circumsphere's).
+static void alpha_cull_boxes(const grt_ctx* c, RenderArgs& a, bool tile_camera_rays, LaunchAux& aux)
+{
+    const grt_ctx* sc = scene_of(c);
+    if (!tile_camera_rays || !c->opt_alpha_cull || c->opt_counters || !sc->gbvh.pbox_a || !alpha_sphere_ok(c, a.p) || !c->erec_alpha_sphere) return;
+    aux.pbox_bundles = a.pbox;
+    a.pbox = sc->gbvh.pbox_a;
+}
 // 11. GRT_DEBUG_LAUNCH: one line per frame on stderr, what the launch is made of; at level 2 the launch order's parts
 static void debug_print_launch(const grt_ctx* c, const RenderArgs& a)
 {
@@ -939,7 +951,8 @@ static int do_launch(grt_ctx* c, RenderArgs& a, void* stream, const AuxOut* px =
     if (want_erec) refresh_eye_records(c, a, s, tile_kernel);                                                          // 9
     LaunchAux aux;
     if ((rc = tile_tuning(c, a, s, tile_kernel, px, aux)) != GRT_OK) return rc;                                        // 10
-    debug_print_launch(c, a);                                                                                          // 11
+    alpha_cull_boxes(c, a, tile_kernel && want_erec, aux);
+    debug_print_launch(c, a);                                                                                    // 11
     if (px && !(tile_kernel && a.mode == 0 && !sc->n_faces)) {                                                         // 12
         // an aux frame on the per-lane kernel (launch_render_aux): screen order, no cost words — and the feedback of this slot starts
         // afresh with the next frame instead of making an order from costs nobody wrote

@@ -38,6 +38,9 @@ struct DevBvh {
                                //   child c of node i at [i*2W + 2c] = (lo.xyz, ref bits), [+1] = (hi.xyz, 0); unused: ref kNoRoot
     float4* pbox = nullptr;    // [n_prims * 2] box of every sorted primitive, (lo.xyz,0)(hi.xyz,r), r = bounding radius about the box centre: what a leaf-range
                                //   child expands to in the tile kernel (built only for the Gaussian BVH)
+    float4* pbox_a = nullptr;  // [n_prims * 2] the same boxes with r = the alpha radius the input boxes carry in lo.w (grt_scene.hip k_proxy_boxes): what
+                               //   the launches whose pre-test reads the alpha sphere cull their leaf ranges with (GRT_OPT_ALPHA_CULL, grt_frame.hip);
+                               //   made, re-made and freed with pbox
     uint32_t* level = nullptr; // [n_prims-1] refit pass in which each node was finished (kept when asked for: refit_lbvh)
     uint32_t* order = nullptr; // [n_prims] sorted position -> input primitive index
     uint32_t n_prims = 0;      // valid primitives (leaves)
@@ -50,7 +53,8 @@ struct DevBvh {
 
 // Build an LBVH over n_in boxes (invalid primitives have lo.x > hi.x and are left out).
 // Returns GRT_OK or an error code (message in *err).
-// want_quad: also build the per-child layout (qnodes, pbox) the tile kernel traverses.
+// want_quad: also build the per-child layout (qnodes, pbox, pbox_a) the tile kernel traverses; d_lo[i].w is then primitive i's alpha radius
+// (pbox_a's hi.w; +inf for a piece), which nothing else reads.
 // keep_levels: keep the per-node refit order so that refit_lbvh can re-fit the boxes of the SAME hierarchy later.
 // size_classes: Gaussian BVH only (GRT_OPT_SIZE_CLASSES of the context that builds).
 int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t leaf_max, bool want_quad, bool keep_levels,
@@ -62,7 +66,7 @@ int build_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, uint32_t l
 // gizmo drag needs (reference: full GAS + IAS rebuild per frame, src/GaussianTracer.cpp:711-794).
 int refit_lbvh(const float4* d_lo, const float4* d_hi, uint32_t n_in, DevBvh* bvh, hipStream_t stream, std::string* err);
 // The Gaussian tree re-fitted to new boxes of its primitives GIVEN IN SORTED ORDER (lb_lo / lb_hi [n_prims]: grt_scene.hip k_refit_prim_boxes):
-// pbox, the binary nodes level by level (bvh->level is derived from the topology when the build did not keep it, and stays), wnodes, qnodes.
+// pbox and pbox_a (lb_lo[j].w = the alpha radius, as for build_lbvh), the binary nodes level by level (bvh->level is derived from the topology when the build did not keep it, and stays), wnodes, qnodes.
 // Queues its work on the stream and does not wait for it.
 int refit_sorted_lbvh(const float4* d_lb_lo, const float4* d_lb_hi, DevBvh* bvh, bool widen_area_only, hipStream_t stream, std::string* err);
 // sum over the binary node records of the half-areas of the two child boxes they hold (0 for a tree without internal nodes): per-workgroup
@@ -194,6 +198,8 @@ struct LaunchAux {
     uint32_t heavy_cap = 0; // grid of the big-window launch (0 = no split)
     bool force_big = false; // GRT_OPT_KERNEL = 4: every block on the big-window kernel (testing)
     const struct AuxOut* px = nullptr; // aux frame (grt_render_aux / grt_render_rays_aux): per-pixel alpha / depth / count
+    const float4* pbox_bundles = nullptr; // set when RenderArgs::pbox is the alpha-radius array (do_launch): the array every stage behind the
+                                          // primary one takes instead — bundles and single rays pre-test on the circumsphere
 };
 // Per-pixel outputs beside colour (grt.h: grt_aux_out).  A second kernel argument of the aux kernels only
 // (k_render_tile_aux, k_render_aux): RenderArgs does not grow, so no existing kernel's code moves.  Each pointer may be null.
@@ -435,6 +441,7 @@ struct grt_ctx {
     // big-window kernel for the heaviest blocks: 0 off, 1 on, 2 auto = on for small launches (<= 3072 blocks: a
     // multi-GPU rank's share of a 1080p frame), where the heaviest tile and not throughput bounds the frame
     int opt_heavy_split = 2;
+    int opt_alpha_cull = 1;     // GRT_OPT_ALPHA_CULL: the leaf cull of uncounted camera-ray frames takes the alpha radius (DevBvh::pbox_a)
     // backward pass (grt_backward.hip): the slot's gradient buffers — one 64-B row per particle, and the 45 higher SH floats of
     // degree >= 1 frames — zero between calls (the flush kernel that adds them into the caller's arrays zeroes them)
     float *d_gacc = nullptr, *d_gacc_sh = nullptr;

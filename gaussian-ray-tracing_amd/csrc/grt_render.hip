@@ -607,6 +607,7 @@ int launch_render(const RenderArgs& a, bool count, int kernel_variant, uint32_t 
         int rc = tile_kernel ? launch_render_tile(a, count, true, 0, stream, err) : launch_render_stream(a, count, true, stream, aux, err);
         if (rc != GRT_OK) return rc;
         RenderArgs b = a;
+        if (aux && aux->pbox_bundles) b.pbox = aux->pbox_bundles; // (the primary stage culled with the alpha radius: LaunchAux)
         b.order = nullptr;
         b.cost = nullptr;
         // the most chunks a queue can hold: one per wave of the primary stage — per 8x8 tile, or per entry of a launch order that

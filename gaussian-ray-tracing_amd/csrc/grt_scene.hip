@@ -19,6 +19,20 @@ using namespace grt;
 // scene kernels
 // ------------------------------------------------------------------------------------------------
 
+// Radius of a sphere about the box centre that holds the particle's alpha ellipsoid |A (x - mu)|^2 = R_a^2, R_a^2 = s^2 (1 +
+// kAlphaSphereRel) + kAlphaSphereAbs being the very sphere the uncounted camera-ray pre-test asks about (grt_device.h:
+// proxy_alpha_sphere_cc): its longest half-axis R_a max(scale), the product's rounding, and emax three times over for the distance
+// between the box centre and mu, as the circumradius beside it.  A tile whose frustum stays outside this sphere has no ray the pre-test
+// would pass, so a leaf step that culls with it (DevBvh::pbox_a) drops only trips that would have ended at the pre-test.
+// ONLY the radius shrinks, never the box: the box's near faces bound every event's distance from below (lam, grt_tile.h) and its far
+// faces decide what a later pass may skip, and the events are the ICOSAHEDRON's — a box fitted to the ellipsoid would let an event of
+// a ray that does pass inside the sphere lie in front of its box, and a pass would call final what is not.
+__device__ __forceinline__ float alpha_cull_radius(float s, const float* __restrict__ scale3, float emax)
+{
+    const float smax = fmaxf(fabsf(scale3[0]), fmaxf(fabsf(scale3[1]), fabsf(scale3[2])));
+    return sqrtf((s * s) * (1.0f + kAlphaSphereRel) + kAlphaSphereAbs) * smax * (1.0f + 1e-5f) + 3.0f * emax;
+}
+
 // World AABB of the proxy icosahedron M = T * (R * diag(scale*s)) (src/GaussianTracer.cpp:304-311,
 // src/geometry/Icosahedron.h:13-37).  opacity <= alpha_min gives s = NaN/0 in the reference, i.e. an
 // unhittable instance: such particles get an inverted box and are left out of the BVH.
@@ -77,9 +91,12 @@ __global__ void k_proxy_boxes(const float* __restrict__ pos, const float* __rest
     }
     // hi.w: radius of a sphere about the BOX CENTRE that holds the proxy (the vertices come in +- pairs, so the box centre is
     // the particle's position up to the rounding the box margin e covers many times over): what the tile kernel's leaf step
-    // culls with besides the box, which for a round proxy reaches 1.5 x as far along an oblique plane normal
-    lo[i] = make_float4(l[0], l[1], l[2], 0.0f);
-    hi[i] = make_float4(h[0], h[1], h[2], sqrtf(r2) * (1.0f + 1e-5f) + 3.0f * emax);
+    // culls with besides the box, which for a round proxy reaches 1.5 x as far along an oblique plane normal.
+    // lo.w: the alpha radius (alpha_cull_radius), which the builder puts in hi.w's place in its second box array.  Never above hi.w: for
+    // s < 0.008 (an opacity within 3e-5 of alpha_min) the absolute part of R_a^2 outgrows the circumsphere, which holds every event there is
+    const float r_circ = sqrtf(r2) * (1.0f + 1e-5f) + 3.0f * emax;
+    lo[i] = make_float4(l[0], l[1], l[2], fminf(alpha_cull_radius(s, scale + i * 3, emax), r_circ));
+    hi[i] = make_float4(h[0], h[1], h[2], r_circ);
 }
 
 // ---- spatial splits of large anisotropic proxies -------------------------------------------------------------------
@@ -207,8 +224,8 @@ __global__ void k_piece_boxes(const float* __restrict__ pos, const float* __rest
     desc[j] = piece_desc(kk, g.p);
     float bl[3], bh[3];
     piece_cell_box(pos, scale, quat, s_arr[i], i, kk, g.p, l, h, bl, bh);
-    plo[j] = make_float4(bl[0], bl[1], bl[2], 0.0f);
-    phi[j] = make_float4(bh[0], bh[1], bh[2], INFINITY); // (a cell has no bounding sphere worth testing: see k_proxy_boxes)
+    plo[j] = make_float4(bl[0], bl[1], bl[2], INFINITY); // (a cell has no bounding sphere worth testing, of either kind: see k_proxy_boxes)
+    phi[j] = make_float4(bh[0], bh[1], bh[2], INFINITY);
 }
 
 // sum over the hittable proxies of log(box diagonal), per workgroup (fixed order; the host adds the partials in double):
@@ -291,7 +308,7 @@ __global__ void k_refit_prim_boxes(const float4* __restrict__ rec, const float* 
     for (int r = 0; r < 3; r++) { kk[r] = (cd >> (10 * r)) & 31u; p[r] = ((cd >> (10 * r + 5)) & 31u) + 1u; } // (piece_desc, grt_device.h)
     float bl[3], bh[3];
     piece_cell_box(pos, scale, quat, s_arr[i], i, kk, p, l, h, bl, bh);
-    lb_lo[j] = make_float4(bl[0], bl[1], bl[2], 0.0f);
+    lb_lo[j] = make_float4(bl[0], bl[1], bl[2], INFINITY);
     lb_hi[j] = make_float4(bh[0], bh[1], bh[2], INFINITY);
 }
 

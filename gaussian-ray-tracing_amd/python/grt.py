@@ -67,7 +67,7 @@ DEBUG_ORDER_PARTS, DEBUG_ORDER_PLAIN, DEBUG_ORDER_QUAD_LIST, DEBUG_ORDER_DILATE 
 
 class MemoryInfo(C.Structure):
     _fields_ = [("scene_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("overflow_pool_bytes", C.c_uint64),
-                ("overflow_chunks", C.c_uint32), ("overflow_demand", C.c_uint32)]
+                ("overflow_chunks", C.c_uint32), ("overflow_demand", C.c_uint32), ("alpha_cull_bytes", C.c_uint64)]
 
 
 class AuxOut(C.Structure):
@@ -217,6 +217,7 @@ OPT_MESH_PRIMARY_WAVE = 37
 OPT_SPLIT_VOL_PCT = 38
 OPT_BWD_PLAIN_ATOMICS = 39
 OPT_REFIT_MAX_AREA_PCT = 40
+OPT_ALPHA_CULL = 41  # the leaf cull of uncounted camera-ray frames takes the alpha radius (include/grt.h); 0: the circumradius, as counted frames do
 ERR_LIMIT = -5
 KERNEL_AUTO, KERNEL_PERLANE, KERNEL_WAVE, KERNEL_STREAM, KERNEL_STREAM_BIG, KERNEL_TILE = 0, 1, 2, 3, 4, 5
 

@@ -132,6 +132,8 @@ typedef struct {
     uint64_t overflow_pool_bytes; /* of which: the tile kernel's pool of window-overflow bags */
     uint32_t overflow_chunks;     /* chunks (32 KiB: 32 entries x 64 rays; a tile takes up to three) in that pool */
     uint32_t overflow_demand;     /* the demand the pool follows: median of what the last eight frames read back asked for */
+    uint64_t alpha_cull_bytes;    /* device memory of the scene's alpha-radius box array (GRT_OPT_ALPHA_CULL), 32 B per primitive of the
+                                     Gaussian BVH; NOT part of scene_bytes, which keeps counting what it has always counted */
 } grt_memory_info;
 
 enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_counters.  A counted frame runs the reference's full event
@@ -254,7 +256,14 @@ enum { GRT_OPT_COUNTERS = 1 /* 1: use the instrumented kernel and fill grt_count
                                            of their k-buffers reduce over the wave first.  Same gradients within the float32 tolerance */,
        GRT_OPT_REFIT_MAX_AREA_PCT = 40  /* grt_update_gaussians_device with GRT_UPDATE_AUTO: a refit that leaves grt_update_info::area_ratio above
                                            value / 100 is followed by a rebuild in the same call (default 200: DESIGN.md 5.9; 0 = never).  A forced
-                                           GRT_UPDATE_REFIT never rebuilds.  Refused on a view.  Culling structure only: same pixels */ };
+                                           GRT_UPDATE_REFIT never rebuilds.  Refused on a view.  Culling structure only: same pixels */,
+       GRT_OPT_ALPHA_CULL = 41          /* 1 (default): the tile kernel's leaf step of an uncounted camera-ray frame (aux frames and the quad
+                                           kernel's parts included) culls a particle with the bounding sphere of its ALPHA ellipsoid
+                                           (response x opacity = alpha_min) instead of its proxy's circumsphere: the particles it no longer
+                                           fetches are those whose trip ended at the pre-test.  A second box array of 32 B per primitive
+                                           (grt_memory_info::alpha_cull_bytes).  Counted frames, bundles, single rays and frames whose
+                                           alpha_min lies below the scene's keep the circumsphere; 0: so does every frame.  Refused on
+                                           nothing; pixels never depend on it */ };
 
 /* ---- context ---- */
 GRT_API int grt_create(grt_ctx** out, int device);
