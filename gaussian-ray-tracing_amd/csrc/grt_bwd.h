@@ -230,6 +230,7 @@ __device__ __forceinline__ void alpha_terms(const BwdArgs& b, uint32_t id, f3 o,
 // transmittance before the event; S: what lies behind it (rad - C_<=i).  Returns whether the geometry / opacity terms were formed.
 // GAUSS: the Gaussians' gradients are wanted at all (else no atomic is in the text); RAYS: the event's part of the ray's gradient
 // goes to ra — m = A^T g_p (v[0..2]) to the origin, d_val m to the direction, the colour's direction derivative to g_dn.
+// GAUSS guards the SH block and NOTHING else: grt_depth_mesh.hip calls event_terms<false, false> for its geometry / opacity terms.
 template <bool GAUSS, bool RAYS>
 __device__ __forceinline__ bool event_terms(const RenderArgs& a, const BwdArgs& b, uint32_t id, f3 o, f3 d, f3 dn, f3 L, float T, float hitAlpha,
                                             f3 S, f3 g_rad, float gAp, float Tend, float v[kVals], RayAcc& ra)

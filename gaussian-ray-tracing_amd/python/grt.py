@@ -160,6 +160,16 @@ class DepthUpstream(C.Structure):
     _fields_ = [("dist", C.c_void_p), ("dist2", C.c_void_p), ("T_out", C.c_void_p)]
 
 
+class DepthMeshOut(C.Structure):
+    """grt_depth_mesh_out (include/grt.h): device pointers of dist / dist2 / weight / count [N], each may be NULL, not all."""
+    _fields_ = [("dist", C.c_void_p), ("dist2", C.c_void_p), ("weight", C.c_void_p), ("count", C.c_void_p)]
+
+
+class DepthMeshUpstream(C.Structure):
+    """grt_depth_mesh_upstream (include/grt.h): device pointers of dloss/ddist, dloss/ddist2 and dloss/dweight [N], each may be NULL, not all."""
+    _fields_ = [("g_dist", C.c_void_p), ("g_dist2", C.c_void_p), ("g_weight", C.c_void_p)]
+
+
 class FeatureGrads(C.Structure):
     """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
@@ -192,6 +202,8 @@ SEGMENT_OUTPUTS = ("radiance", "T_out", "depth", "count")
 DEPTH_OUTPUTS = ("dist", "dist2", "T_out", "count")
 DEPTH_KINDS = {"key": 0, "peak": 1}  # GRT_DEPTH_KEY, GRT_DEPTH_PEAK
 DEPTH_GROUPS = ("pos", "scale", "quat", "opacity")
+DEPTH_MESH_OUTPUTS = ("dist", "dist2", "weight", "count")
+DEPTH_SURFACE = 1  # GRT_DEPTH_SURFACE
 
 
 class Mesh(C.Structure):
@@ -233,6 +245,7 @@ EXPORTS = [
     "grt_backward_events_mesh_frame", "grt_backward_events_mesh_rays",
     "grt_trace_segments_frame", "grt_trace_segments_rays", "grt_backward_segments_frame", "grt_backward_segments_rays",
     "grt_ray_depth_frame", "grt_ray_depth_rays", "grt_backward_depth_frame", "grt_backward_depth_rays",
+    "grt_ray_depth_mesh_frame", "grt_ray_depth_mesh_rays", "grt_backward_depth_mesh_frame", "grt_backward_depth_mesh_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_render_features_mesh_frame", "grt_render_features_mesh_rays",
     "grt_backward_features_mesh_frame", "grt_backward_features_mesh_rays", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
@@ -316,6 +329,12 @@ def lib():
         L.grt_ray_depth_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.c_int, C.POINTER(DepthOut), vp]
         L.grt_backward_depth_frame.argtypes = [vp, C.POINTER(Params), C.c_int, C.POINTER(DepthUpstream), C.POINTER(BackwardOut), u32, u32, u32, u32, vp]
         L.grt_backward_depth_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.c_int, C.POINTER(DepthUpstream), C.POINTER(BackwardOut), vp]
+        L.grt_ray_depth_mesh_frame.argtypes = [vp, C.POINTER(Params), C.c_int, u32, C.POINTER(DepthMeshOut), u32, u32, u32, u32, u32, u32, vp]
+        L.grt_ray_depth_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.c_int, u32, C.POINTER(DepthMeshOut), u32, u32, vp]
+        L.grt_backward_depth_mesh_frame.argtypes = [vp, C.POINTER(Params), C.c_int, u32, C.POINTER(DepthMeshUpstream), C.POINTER(FeatureGrads),
+                                                    u32, u32, u32, u32, u32, u32, vp]
+        L.grt_backward_depth_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, C.c_int, u32, C.POINTER(DepthMeshUpstream),
+                                                   C.POINTER(FeatureGrads), u32, u32, vp]
         L.grt_render_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, u32, u32, u32, u32, vp]
         L.grt_render_features_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, vp]
         L.grt_backward_features_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, vp]
@@ -1280,6 +1299,73 @@ class Tracer:
         else:
             self._check(lib().grt_backward_depth_frame(self._h, C.byref(params), kind, C.byref(up), C.byref(out), x0, y0, x1, y1,
                                                        self._stream()))
+        return into
+
+    def ray_depth_mesh(self, params, rays=None, window=None, kind="peak", outputs=DEPTH_MESH_OUTPUTS, steps=None, surface=False):
+        """grt_ray_depth_mesh_frame / grt_ray_depth_mesh_rays (rays [n][6] given): ray_depth() of a frame whose rays bounce off the
+        meshes set on the tracer (include/grt.h) -> dict of torch tensors [n] or [h][w] on the tracer's GPU: 'dist', 'dist2', 'weight'
+        and 'count' (uint32).  An event of iteration s lies at the path prefix P_s (the sum of the earlier iterations' segment ends)
+        plus its own distance on the step's ray (kind "key" or "peak"), and enters with the colour weight c_s * T_i * alpha_i;
+        dist / weight is the mean path length of what the pixel shows.  steps = (first, last) as in render_features_mesh; surface:
+        a terminating hit of a NORMAL mesh adds its own surface with 1 - D.  On a tracer without meshes dist is (1 - T_out) *
+        ray_depth()'s.  An untraced ray and a pixel outside a window hold zeros.  Bitwise reproducible."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, kind = self._depth_inputs("ray_depth_mesh", params, rays, window, kind)
+        first, last = self._mesh_steps("ray_depth_mesh", steps)
+        outputs = tuple(outputs)
+        if not outputs or any(k not in DEPTH_MESH_OUTPUTS for k in outputs):
+            raise GrtError(f"ray_depth_mesh: outputs must be a non-empty subset of {DEPTH_MESH_OUTPUTS}, not {outputs}")
+        out = {k: (t.zeros(shape, dtype=t.int32, device=dev).view(t.uint32) if k == "count" else t.zeros(shape, dtype=t.float32, device=dev))
+               for k in DEPTH_MESH_OUTPUTS if k in outputs}
+        if not shape[0] or not shape[-1]:  # (no ray: nothing to write.  An empty scene goes to the library: its refusals hold)
+            return out
+        ptrs = DepthMeshOut(*(out[k].data_ptr() if k in out else None for k in DEPTH_MESH_OUTPUTS))
+        flags = DEPTH_SURFACE if surface else 0
+        if rays is not None:
+            self._check(lib().grt_ray_depth_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], kind, flags, C.byref(ptrs), first, last,
+                                                      self._stream()))
+        else:
+            self._check(lib().grt_ray_depth_mesh_frame(self._h, C.byref(params), kind, flags, C.byref(ptrs), first, last, x0, y0, x1, y1,
+                                                       self._stream()))
+        return out
+
+    def backward_depth_mesh(self, params, grad_dist=None, grad_dist2=None, grad_weight=None, rays=None, window=None, kind="peak", into=None,
+                            groups=None, steps=None, surface=False):
+        """grt_backward_depth_mesh_frame / grt_backward_depth_mesh_rays: grad_dist, grad_dist2, grad_weight [n] or [h][w] (each may be
+        None, not all) hold dloss/ddist, dloss/ddist2 and dloss/dweight of what ray_depth_mesh computed (same params, rays / window,
+        kind, steps, surface) -> dict of torch tensors pos, scale, quat, opacity: the gradients with respect to the uploaded Gaussians,
+        allocated zeroed for `groups` (default: all four) or ACCUMULATED into the tensors of `into`.  The meshes, the path and its
+        prefix are held fixed; nothing is computed for rays or the camera.  A ray whose three upstream values are exactly 0 is not
+        traced; include/grt.h."""
+        t = self._torch
+        rays, shape, (x0, y0, x1, y1), dev, kind = self._depth_inputs("backward_depth_mesh", params, rays, window, kind)
+        first, last = self._mesh_steps("backward_depth_mesh", steps)
+        ups = []
+        for name, g in (("grad_dist", grad_dist), ("grad_dist2", grad_dist2), ("grad_weight", grad_weight)):
+            if g is not None and (not t.is_tensor(g) or tuple(g.shape) != shape):
+                raise GrtError(f"backward_depth_mesh: {name} must be a tensor of shape {list(shape)}")
+            ups.append(g.detach().to(dev, t.float32).contiguous() if g is not None else None)
+        if all(g is None for g in ups):
+            raise GrtError("backward_depth_mesh: no upstream (grad_dist, grad_dist2 and grad_weight are all None)")
+        if any(k not in DEPTH_GROUPS for k in (groups or ())) or any(k not in DEPTH_GROUPS for k in (into or ())):
+            raise GrtError(f"backward_depth_mesh: the gradient groups are {DEPTH_GROUPS} (the depth has no colour)")
+        if groups is None and into is None:
+            groups = DEPTH_GROUPS
+        if (into is not None and not into) or (into is None and not len(groups)):
+            raise GrtError("backward_depth_mesh: no gradient group asked for")
+        into, hold = self._grad_buffers(into, groups, dev)
+        n = self._scene.n_particles if self._scene is not None else self.n_particles
+        if not shape[0] or not shape[-1] or not n:  # (no ray or no particle: nothing to add)
+            return into
+        ptrs = FeatureGrads(hold.pos, hold.scale, hold.quat, hold.opacity, None)
+        up = DepthMeshUpstream(*(g.data_ptr() if g is not None else None for g in ups))
+        flags = DEPTH_SURFACE if surface else 0
+        if rays is not None:
+            self._check(lib().grt_backward_depth_mesh_rays(self._h, C.byref(params), rays.data_ptr(), shape[0], kind, flags, C.byref(up),
+                                                           C.byref(ptrs), first, last, self._stream()))
+        else:
+            self._check(lib().grt_backward_depth_mesh_frame(self._h, C.byref(params), kind, flags, C.byref(up), C.byref(ptrs), first, last,
+                                                            x0, y0, x1, y1, self._stream()))
         return into
 
     def _feature_inputs(self, what, params, feat, rays, window):

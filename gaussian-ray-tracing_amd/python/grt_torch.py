@@ -513,7 +513,70 @@ class _RayDepth(torch.autograd.Function):
         return out + (g_rays, g_cam, None, None, None, None)
 
 
-def ray_depth(tracer, params, geometry=None, rays=None, camera=None, kind="peak", window=None):
+class _RayDepthMesh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, scale, quat, opacity, rays, window, kind, steps, surface, tracer, params):
+        # pos .. opacity: the tensors of the tracer's last upload: only the carriers of the geometry gradients
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.params, ctx.window, ctx.kind, ctx.steps, ctx.surface = tracer, params, window, kind, steps, surface
+        ctx.rays = rays.detach().to(f"cuda:{tracer.device}", torch.float32).contiguous() if rays is not None else None
+        ctx.like = tuple((t.device, t.dtype) for t in (pos, scale, quat, opacity))
+        out = tracer.ray_depth_mesh(params, rays=ctx.rays, window=window, kind=kind, steps=steps, surface=surface)
+        ctx.mark_non_differentiable(out["count"])
+        return out["dist"], out["dist2"], out["weight"], out["count"]
+
+    @staticmethod
+    def backward(ctx, g_D, g_D2, g_W, g_count):
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("pos", "scale", "quat", "opacity")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:4]) if want]
+        ups = [g.to(f"cuda:{tr.device}", torch.float32).contiguous() if g is not None else None for g in (g_D, g_D2, g_W)]
+        if not groups or all(g is None for g in ups):
+            return (None,) * 11
+        g = tr.backward_depth_mesh(ctx.params, *ups, rays=ctx.rays, window=ctx.window, kind=ctx.kind, groups=groups, steps=ctx.steps,
+                                   surface=ctx.surface)
+        return tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like)) + (None,) * 7
+
+
+def _ray_depth_mesh(tracer, params, geometry, rays, camera, kind, window, steps, surface):
+    """ray_depth(..., through_meshes=True): the checks and the call."""
+    if kind not in grt.DEPTH_KINDS:
+        raise ValueError(f"grt_torch.ray_depth: kind must be one of {tuple(grt.DEPTH_KINDS)}, not {kind!r}")
+    if rays is not None and (not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] != 6):
+        raise ValueError(f"grt_torch.ray_depth: rays must be a tensor of shape [n][6], not {tuple(rays.shape) if torch.is_tensor(rays) else type(rays)}")
+    if (rays is not None and rays.requires_grad) or (camera is not None and any(t.requires_grad for t in camera)):
+        raise ValueError("grt_torch.ray_depth: gradients with respect to rays or the camera are not computed through meshes (nor through "
+                         "the path or its prefix); detach rays and camera")
+    if camera is not None:
+        if rays is not None:
+            raise ValueError("grt_torch.ray_depth: rays and camera exclude each other")
+        params = type(params).from_buffer_copy(params)
+        for name, t in zip(("eye", "U", "V", "W"), camera):
+            v = t.detach().to("cpu", torch.float32).reshape(3)
+            for k in range(3):
+                getattr(params, name)[k] = float(v[k])
+    if geometry is None:
+        with torch.no_grad():
+            out = tracer.ray_depth_mesh(params, rays=rays, window=window, kind=kind, steps=steps, surface=bool(surface))
+        return tuple(out[k] for k in grt.DEPTH_MESH_OUTPUTS)
+    gs = tuple(geometry)
+    scene = tracer._scene if tracer._scene is not None else tracer  # (a view renders its parent's scene)
+    n = scene.n_particles
+    want = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,)}
+    if len(gs) != 4 or any(not torch.is_tensor(t) for t in gs):
+        raise ValueError("grt_torch.ray_depth: geometry must be four tensors (pos, scale, quat, opacity)")
+    for (name, shape), t in zip(want.items(), gs):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"grt_torch.ray_depth: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
+                             f"not {tuple(t.shape)}")
+    return _RayDepthMesh.apply(*gs, rays, window, kind, steps, bool(surface), tracer, params)
+
+
+def ray_depth(tracer, params, geometry=None, rays=None, camera=None, kind="peak", window=None, through_meshes=False, steps=None, surface=False):
     """(dist, dist2, T_out, count) of every whole ray (Tracer.ray_depth; include/grt.h: grt_ray_depth_frame / _rays):
     dist = sum w_i tau_i, dist2 = sum w_i tau_i^2, T_out = prod (1 - alpha_i) and the event count, with tau_i the distance of the
     particle's maximum response along the ray (kind "peak") or the event's key distance (kind "key": the aux depth, whose distances
@@ -526,7 +589,19 @@ def ray_depth(tracer, params, geometry=None, rays=None, camera=None, kind="peak"
     It traces the scene the tracer HOLDS and uploads nothing, like trace_segments: the `geometry` tensors only carry the gradient —
     they must be the tensors of the tracer's last upload, their shapes are checked against the tracer's particle count and their
     values are not read.  The backward raises GrtError when the tracer has received another upload since the forward.  A tracer with
-    meshes: ValueError (the ray depth is the Gaussian-only call)."""
+    meshes: ValueError (the ray depth is the Gaussian-only call).
+    through_meshes=True sends the call to Tracer.ray_depth_mesh / backward_depth_mesh (grt_ray_depth_mesh_*, grt_backward_depth_mesh_*;
+    DESIGN.md 5.26) and returns (dist, dist2, weight, count): the rays bounce as the frame's do, an event of iteration s lies at the
+    path prefix P_s plus its own distance on the step's ray and enters with the colour weight c_s w_i; dist / weight is the mean path
+    length of what the pixel shows.  steps=(first, last) counts only the events of these iterations (1-based, inclusive, last None =
+    open; (2, None): what is seen only through a bounce); surface=True adds a terminating NORMAL hit's own surface.  dist, dist2 and
+    weight are differentiable with respect to `geometry` with the meshes, the path and its prefix held fixed; gradients with respect
+    to rays, the camera, the path and P_s are NOT computed (`rays` or `camera` that require grad: ValueError).  The flag alone is the
+    switch: `steps` or `surface` given without it raise ValueError."""
+    if (steps is not None or surface) and not through_meshes:
+        raise ValueError("grt_torch.ray_depth: steps and surface are arguments of the mesh call; pass through_meshes=True with them")
+    if through_meshes:
+        return _ray_depth_mesh(tracer, params, geometry, rays, camera, kind, window, steps, surface)
     if tracer.has_meshes:
         raise ValueError("grt_torch.ray_depth: meshes are set on this tracer; the ray depth is the Gaussian-only call")
     if kind not in grt.DEPTH_KINDS:

@@ -1066,6 +1066,72 @@ GRT_API int grt_backward_depth_frame(grt_ctx* ctx, const grt_params* p, int kind
                                      const grt_backward_out* out, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
 GRT_API int grt_backward_depth_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, int kind,
                                     const grt_depth_upstream* up, const grt_backward_out* out, void* stream);
+/* ---- differentiable ray depth of MESH frames: path length through mirrors and glass, with gradients ----
+ * The depth calls above for a scene with meshes set (a LiDAR or monocular-depth loss on what a reflection shows, a depth-variance
+ * regulariser behind glass, a depth map that includes an opaque mesh's own surface).  A ray runs iterations s = 1..S exactly as
+ * documented at grt_backward_mesh and grt_render_features_mesh_frame: its own ray (o_s, d_s) per iteration, its segment
+ * [t_min, tmax_s] (tmax_s: the mesh hit distance, for glass with the refraction shift, or t_max), ONE event list with ONE running
+ * transmittance carried through `density`, and the segment's colour weight
+ *     c_s = 1 - A_{s-1}   Gaussian pass;     D_S (1 - B_{S-1})   last pass;     1   a terminating GRT_NORMAL hit.
+ * PATH PREFIX.  P_1 = 0, P_{s+1} = P_s + tmax_s, a float32 running sum per ray.  It is DATA: the mesh hit, its normal and the next
+ * ray are held fixed, as in grt_backward_mesh.  Distances are in units of each step's own |d_s|, as the picks' t is.
+ * An event i of segment s lies at x_i = P_s + tau_i, with tau_i the event's key distance (GRT_DEPTH_KEY) or the peak distance d_val on
+ * the step's ray (o_s, d_s) (GRT_DEPTH_PEAK), and w_i = T_i alpha_i.
+ *   step_first, step_last   as for grt_render_features_mesh_frame: 1-based, inclusive; 0, 0 = all; step_last = 0 leaves the range
+ *                  open.  An event outside the range is composited — T, A and B run through it — but contributes to no output and
+ *                  is not counted.  (2, 0) measures what is seen only through a bounce.
+ * FORWARD.  Per segment, in compositing order, float32 without contraction, before T is updated:
+ *     m0 += w;   wt = w * x;   m1 += wt;   m2 += wt * x
+ * and at the iteration's step   weight += m0 * c_s;   dist += m1 * c_s;   dist2 += m2 * c_s.
+ *   flags   GRT_DEPTH_SURFACE: a terminating (GRT_NORMAL) hit whose step is in range adds the surface itself, as the colour adds
+ *           ncol (1 - D_S): with u = 1 - D_S and x_S = P_S + tmax_S,  weight += u;  dist += u * x_S;  dist2 += (u * x_S) * x_S.
+ *   out     dist, dist2, weight (float32 [N]) and count (uint32 [N], the counted events); each may be NULL, not all.  dist / weight
+ *           is the mean path length of what the pixel shows.  An untraced ray writes 0, 0, 0, 0; every element of the window or of
+ *           the buffer is WRITTEN once per requested array.  No atomic, no wave operation: BITWISE reproducible, and windows tile
+ *           a frame bit for bit.  With surface off, weight is grt_render_features_mesh_frame's output for feat = 1, bit for bit.
+ * A context WITHOUT meshes is served: every ray then has one last pass, so dist = (1 - T_out) dist_plain and weight = (1 - T_out)^2.
+ * BACKWARD of loss = sum_ray g_D dist + g_D2 dist2 + g_W weight; each upstream may be NULL (zero), not all; every discrete decision
+ * held fixed.  A ray whose three upstream values are exactly 0 is not traced.  For a counted event phi_i = g_D x_i + (g_D2 x_i) x_i +
+ * g_W, and 0 otherwise; dloss/dalpha_i is grt_backward_features_mesh_frame's with phi_i as its one-channel radiance.  Under
+ * GRT_DEPTH_SURFACE a counted terminating step has phi_surf = g_D x_S + g_D2 x_S^2 + g_W, which enters as grt_backward_mesh's ncol
+ * term does (gD_S = -phi_surf); the surface has no alpha of its own.  Under PEAK a counted event additionally has
+ *     dloss/dtau_i = c_s w_i (g_D + 2 g_D2 x_i),
+ * NOT gated by the 0.99 clamp, down to pos, scale and quat on (o_s, d_s) as in grt_backward_depth_frame.  Under KEY the distances are
+ * data.  Gradients are ADDED by original id into grads->pos, scale, quat, opacity through the context's gradient buffer and its flush
+ * (float atomics; GRT_OPT_BWD_PLAIN_ATOMICS applies); grads->feat is left untouched and is no request, and no sh is touched.
+ * Both: asynchronous on `stream`; grt_last_kernel_ms reports the call's device time; a view computes its scene's result; the
+ * forward uses no buffer of the context.  With no rays, no particles or an empty tree the calls return GRT_OK: the forward writes
+ * zeros, the backward nothing.
+ * Refused with GRT_ERR_INVALID (the entry point's name in front; the context stays usable): what the feature calls of mesh frames
+ * refuse (NULL p, no BVH, GRT_OPT_COUNTERS = 1, sh_degree_max > 3, t_min <= 0, p->type outside MIRROR/NORMAL/GLASS, step_first >
+ * step_last with step_last != 0, a window outside the frame, a NULL ray buffer), an unknown kind, unknown flag bits, no output
+ * (forward: out NULL or all four arrays NULL; backward: grads NULL or pos, scale, quat and opacity all NULL), no upstream (up NULL or
+ * all three NULL).  GRT_ERR_LIMIT as in the mesh backward.
+ * NOT computed: gradients with respect to rays or the camera, gradients through the path (the mesh hit, its normal, the next ray),
+ * gradients through P_s. */
+#define GRT_DEPTH_SURFACE 1u
+typedef struct grt_depth_mesh_out {      /* device pointers, each may be NULL, not all */
+    float* dist;                         /* [N]  sum_s c_s sum_{i in s} w_i x_i (+ the surface) */
+    float* dist2;                        /* [N]  sum_s c_s sum_{i in s} w_i x_i^2 (+ the surface) */
+    float* weight;                       /* [N]  sum_s c_s sum_{i in s} w_i (+ the surface) */
+    uint32_t* count;                     /* [N]  counted events */
+} grt_depth_mesh_out;
+typedef struct grt_depth_mesh_upstream { /* device pointers, [N] float32 each; each may be NULL (zero), not all */
+    const float* g_dist;
+    const float* g_dist2;
+    const float* g_weight;
+} grt_depth_mesh_upstream;
+GRT_API int grt_ray_depth_mesh_frame(grt_ctx* ctx, const grt_params* p, int kind, uint32_t flags, const grt_depth_mesh_out* out,
+                                     uint32_t step_first, uint32_t step_last, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                                     void* stream);
+GRT_API int grt_ray_depth_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, int kind, uint32_t flags,
+                                    const grt_depth_mesh_out* out, uint32_t step_first, uint32_t step_last, void* stream);
+GRT_API int grt_backward_depth_mesh_frame(grt_ctx* ctx, const grt_params* p, int kind, uint32_t flags,
+                                          const grt_depth_mesh_upstream* up, const grt_feature_grads* grads, uint32_t step_first,
+                                          uint32_t step_last, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, void* stream);
+GRT_API int grt_backward_depth_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, int kind, uint32_t flags,
+                                         const grt_depth_mesh_upstream* up, const grt_feature_grads* grads, uint32_t step_first,
+                                         uint32_t step_last, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
