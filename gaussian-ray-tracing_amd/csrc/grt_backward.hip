@@ -4,7 +4,7 @@
 // The device text is grt_bwd.h; this unit instantiates k_backward<MERGE> from it and holds what exists once for the three backward
 // units: the flush kernels, the context's gradient buffers, and the host path every entry point takes (grt_internal.h: bwd_fill_args,
 // bwd_launch; the work mappings set_window and set_rays are grt_frame.hip's) — and, for grt_stats.hip and grt_features.hip as well,
-// the launch of a one-ray-per-lane kernel (lane_launch, lane_launch_done).
+// the launch of a one-ray-per-lane kernel (lane_launch, lane_launch_done), and the mesh units' step-range refusal (check_step_range).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -128,6 +128,13 @@ int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, con
     a->swizzle_chunk = (uint32_t)c->opt_swizzle;
     a->err_word = c->d_err;
     return GRT_OK;
+}
+
+int check_step_range(grt_ctx* c, uint32_t step_first, uint32_t step_last, const char* fn)
+{
+    if (step_last == 0u || step_first <= step_last) return GRT_OK;
+    c->err = std::string(fn) + ": step_first > step_last (iterations are counted from 1; step_last = 0 leaves the range open)";
+    return GRT_ERR_INVALID;
 }
 
 int lane_launch(grt_ctx* c, const RenderArgs& a, const void* kernel, void** args, hipStream_t s, const char* fn)

@@ -10,6 +10,9 @@
 //   sweep 1  walks the same loop and the same events and forms every composited event's terms, its two suffix quantities
 //            (the weighted radiance behind it, sum_{j >= s} gD_j T_end,j) as total minus prefix.
 // Nothing is stored per segment or per iteration: a glass ray may take 1001 iterations.
+// The bounce loop stays WRITTEN OUT here, as backward_body's sweep does (this kernel runs under every training step
+// through a mirror).  Its one other text is mesh_walk of grt_mesh_walk.h, which every other mesh unit stands on: a
+// change here is a change there, and the colour weight c_s below is seg_weight's.
 //
 // The totals (iterations 1..S; every iteration but the last is a Gaussian pass, and in Gaussian passes B follows A step by step):
 //   e     the last Gaussian pass before the A clamp binds (all of them when it never binds)

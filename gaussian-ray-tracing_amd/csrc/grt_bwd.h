@@ -1,8 +1,9 @@
 // grt_bwd.h — the device text the units that walk a ray's composited events share (grt_backward.hip, grt_backward_rays.hip,
-// grt_backward_mesh.hip, grt_stats.hip, grt_stats_mesh.hip, grt_features.hip, grt_picks.hip, grt_events.hip, grt_segments.hip; DESIGN.md 5.8,
-// 5.10, 5.11, 5.12, 5.17, 5.18, 5.19, 5.20, 5.21, 5.22): the kernels' arguments, a
+// grt_backward_mesh.hip, grt_stats.hip, grt_features.hip, grt_picks.hip, grt_events.hip, grt_segments.hip, and through grt_mesh_walk.h the
+// five *_mesh feature units): the kernels' arguments, a
 // lane's ray and upstream gradient, the sweep over a ray segment's composited events as a helper (sweep_events: the statistics, the
-// feature, the pick and the event-list kernels call it; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
+// feature, the pick and the event-list kernels call it, and mesh_walk of grt_mesh_walk.h once per iteration of a mesh frame's raygen
+// loop; backward_body and k_backward_mesh keep the same loop written out, DESIGN.md 5.18 says why), the ONE
 // grouping of a wave's lanes by particle (wave_groups), the terms of one composited event (event_terms, and below one alpha: alpha_terms),
 // the scatter into the gradient buffer, and the ONE body of k_backward<MERGE> and k_backward_rays<MERGE, GAUSS>.
 //
@@ -333,11 +334,17 @@ __device__ __forceinline__ bool load_upstream(const BwdArgs& b, size_t idx, bool
 // trip count, and a lane whose own condition is false idles inside them with `act` cleared.  The round itself is the per-lane
 // gps_round inside `if (act)`, with no wave operation in it.  A lane's rounds are bounded by lastT rising past the segment's end:
 // the ballot becomes zero.  A caller that loops around the sweep (passes) enters and leaves its loops the same way.
-// backward_body, k_backward_mesh and k_particle_stats_mesh hold this loop written out, statement for statement: a change here is a
-// change there.
-template <class OnSlot>
+// leave() (optional, per lane, no wave operation): asked between two rounds of a lane that was still in the sweep; true takes the lane
+// out of it (`act` cleared).  grt_mesh_walk.h hands it on for k_backward_events_mesh; every other caller leaves it defaulted.
+// backward_body, k_backward_mesh and the mesh kernels that grt_mesh_walk.h's head lists as left out (k_ray_events_mesh,
+// k_render_features_mesh, k_backward_features_mesh, k_backward_depth_mesh) hold this loop written out, statement for statement: a change
+// here is a change there.  The mesh frames' raygen loop around the sweep is mesh_walk of grt_mesh_walk.h.
+struct NeverLeave {
+    __device__ __forceinline__ bool operator()() const { return false; }
+};
+template <class OnSlot, class Leave = NeverLeave>
 __device__ __forceinline__ void sweep_events(const RenderArgs& a, uint32_t* stk, f3 o, f3 d, const rayinv& ri, float t_max, bool part, float& T,
-                                             OnSlot&& on_slot)
+                                             OnSlot&& on_slot, Leave&& leave = Leave())
 {
     const float epsT = 1e-9f;
     const float t_hi = t_max + epsT;
@@ -377,6 +384,7 @@ __device__ __forceinline__ void sweep_events(const RenderArgs& a, uint32_t* stk,
             if (kb.key[K - 1] == kKeyInvalid) act = false;
             else last_key = kb.key[K - 1];
             act = act && (lastT <= t_max) && (T > minT);
+            if (leave()) act = false;
         }
     }
 }

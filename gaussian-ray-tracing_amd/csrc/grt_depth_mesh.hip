@@ -9,43 +9,33 @@
 // The step filter (step_first, step_last) is a per-lane predicate on the iteration's number: an event outside the range is composited —
 // T, A and B run through it — and enters no output; it changes no control flow.  The surface flag likewise touches only the step.
 //
-// Both kernels: one ray per lane, an 8x8 tile or 64 buffer rays per wave.
-//   k_ray_depth_mesh<PEAK>              ONE sweep: k_render_features_mesh's raygen loop, statement for statement, with the three moment
-//                                       accumulators in place of Phi.  Plain stores at the end; no atomic, no wave operation.
-//   k_backward_depth_mesh<MERGE, PEAK>  two sweeps: k_backward_features_mesh<MERGE, ., true>'s loop with the one-channel radiance
+// Both kernels: one ray per lane, an 8x8 tile or 64 buffer rays per wave (grt_mesh_walk.h: the raygen loop, its convergence contract
+// and why it cannot hang).  peak_tau / tau_terms (grt_depth.h) run per lane and hold no wave operation.
+//   k_ray_depth_mesh<PEAK>              on mesh_walk, ONE sweep, with three moment accumulators per segment.  Plain stores at the end; no
+//                                       atomic, no wave operation.
+//   k_backward_depth_mesh<MERGE, PEAK>  keeps the loop WRITTEN OUT as it had it, its own step filter included, statement for statement mesh_walk's and sweep_events' (a change there
+//                                       is a change here): on mesh_walk its merged PEAK instantiation ran 2 % behind the parent's
+//                                       (DESIGN.md 5.27).  Two sweeps: k_backward_features_mesh<MERGE, ., true>'s with the one-channel radiance
 //                                       phi_i = g_D x_i + (g_D2 x_i) x_i + g_W (0 outside the step range), no feature scatter; the
 //                                       surface enters sweep 0's F total as -phi_surf T_end,S (k_backward_mesh's ncol term); under PEAK
 //                                       a counted event adds dloss/dtau_i = c_s w_i (g_D + 2 g_D2 x_i) through tau_terms<false> on the
-//                                       step's ray, NOT gated by the 0.99 clamp.  scatter<MERGE> writes the 11 geometry / opacity
-//                                       values into the slot's gradient buffer.
-//
-// Wave convergence: scatter<MERGE> (DPP, v_readlane) is reached by every lane of the wave for every slot of every round of every
-// iteration: it sits outside every per-lane `if`.  The three nested loops (iterations, rounds, slots) are each entered and left on a
-// wave-uniform condition — a ballot over the lanes' own conditions, or a constant trip count — and a lane whose own condition is
-// false idles inside them with `it` / `act` cleared, as the header of grt_backward_mesh.hip states.  The mesh walk is the per-lane
-// mesh_closest_t, the k-nearest round the per-lane gps_round, and peak_tau / tau_terms (grt_depth.h) run per lane; all sit inside
-// `if (it)` / `if (act)` and none holds a wave operation.  Why it cannot hang: a lane's iterations are bounded by max_bounces and the
-// 1000-iteration timeout, its rounds by lastT rising past the segment's end (a round that finds nothing clears `act`), the slot loop
-// runs K times, and the group loop of wave_groups clears at least its leader's bit of a ballot per turn — every ballot becomes zero.
-// Only vector stores and vector atomics write memory.
+//                                       step's ray, NOT gated by the 0.99 clamp.  scatter<MERGE> (DPP, v_readlane; outside
+//                                       every per-lane `if`) writes the 11 geometry / opacity values into the slot's gradient buffer.
 #include <string>
 
-#include "grt_bwd.h"
 #include "grt_depth.h"
-#include "grt_mesh.h"
+#include "grt_mesh_walk.h"
 
 namespace grt {
 namespace {
 
-static_assert(kBlock == kRoundBlock, "the mesh depth kernels run gps_round (grt_kround.h): its per-lane stack stride is the launch block size");
-
-// first..last: the iterations whose events are counted, 1-based, inclusive; last = 0: open.  surface: GRT_DEPTH_SURFACE
+// steps / first..last: the iterations whose events are counted, 1-based, inclusive (last = 0: open).  surface: GRT_DEPTH_SURFACE
 struct DepthMeshFwd {
     const float* pos;   // [n][3] by original id (the uploaded attributes; read under PEAK alone)
     const float* scale; // [n][3]
     const float* quat;  // [n][4]
     grt_depth_mesh_out o;
-    uint32_t first, last;
+    StepRange steps;
     uint32_t surface;
 };
 struct DepthMeshBwd {
@@ -70,116 +60,46 @@ __global__ __launch_bounds__(kBlock) void k_ray_depth_mesh(const RenderArgs a, c
     uint32_t n = 0u;
 
     if (__builtin_amdgcn_ballot_w64(live)) { // wave-uniform
-        const float epsT = 1e-9f;
-        const float minT = a.p.minTransmittance;
-        const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
-        KBuf<K> kb;
-        grt::Cnt cnt; // (dead: no counters, no watchdog)
-
-        f3 curO = o, curD = d;
-        float A = 0.0f, B = 0.0f, density = 0.0f;
         float Pfx = 0.0f; // the path prefix P_s
-        uint32_t numBounces = 0u, timeout = 0u, step = 0u;
-        bool going = live;
-        // ---- the raygen loop (shaders/tracer.cu:58-106), the whole wave in step ----
-        while (true) {
-            const bool it = going && (length3(curD) > 0.1f) && (numBounces < a.p.max_bounces);
-            going = it;
-            if (!__builtin_amdgcn_ballot_w64(it)) break; // wave-uniform
-            const f3 ray_o = curO, ray_d = curD;
-            int state = LastGaussianPass;
-            float seg_tmax = a.p.t_max;
-            f3 normal = mk3(0, 0, 0);
-            if (it) { // per lane: no wave operation inside
-                uint32_t n0 = 0, n1 = 0;
-                const MeshHit mh = mesh_closest_t<false, kBlock>(a, stk, ray_o, ray_d, kTraceMeshTmin, kTraceMeshTmax, n0, n1);
-                mesh_shade(a, mh, ray_o, ray_d, state, seg_tmax, normal, curO, curD, numBounces);
-                step++;
-            }
-            // ---- this iteration's Gaussian segment [t_min, seg_tmax] on (ray_o, ray_d), T carried on (trace(), tracer.cuh:328-373) ----
-            const rayinv ri = mk_rayinv(ray_o, ray_d);
-            const float t_hi = seg_tmax + epsT;
-            float T = 1.0f - density, lastT = a.p.t_min;
-            uint64_t last_key = key0;
-            const bool counted = (step >= k.first) && (k.last == 0u || step <= k.last);
-            float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
-            bool act = it && (lastT <= seg_tmax) && (T > minT);
-            while (__builtin_amdgcn_ballot_w64(act)) {
-                if (act) {
-                    gps_round<false, false, K>(a, stk, ray_o, ray_d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
-                    if (kb.key[0] == kKeyInvalid) act = false;
-                }
-#pragma unroll 1
-                for (int i = 0; i < K; i++) {
-                    bool hit = false;
-                    uint32_t id = 0;
-                    uint64_t key = kKeyInvalid;
-                    float hitAlpha = 0.0f;
-#pragma unroll
-                    for (int j = 0; j < K; j++) {
-                        if (j == i) { key = kb.key[j]; hitAlpha = kb.alpha[j]; }
+        float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
+        bool counted = false;
+        mesh_walk(
+            a, stk, o, d, live,
+            [&](const MeshSeg& s) {
+                counted = k.steps.counted(s.step);
+                m0 = 0.0f; m1 = 0.0f; m2 = 0.0f;
+            },
+            [&](const MeshSeg& s, bool hit, uint32_t id, float T, float hitAlpha, uint64_t key) {
+                if (hit && counted) {
+                    float tau = key_t(key);
+                    if (PEAK) {
+                        PeakFrame f;
+                        tau = peak_tau(k.pos, k.scale, k.quat, id, s.ray_o, s.ray_d, f);
                     }
-                    if (act && key != kKeyInvalid && T > minT) {
-                        lastT = fmaxf(key_t(key), lastT);
-                        if (a.p.alpha_min < hitAlpha) {
-                            hit = true;
-                            id = key_id(key);
-                        }
-                    }
-                    if (hit && counted) {
-                        float tau = key_t(key);
-                        if (PEAK) {
-                            PeakFrame f;
-                            tau = peak_tau(k.pos, k.scale, k.quat, id, ray_o, ray_d, f);
-                        }
-                        const float x = Pfx + tau;
-                        const float w = T * hitAlpha; // T: the transmittance before the event
-                        const float wt = w * x;
-                        m0 = m0 + w;
-                        m1 = m1 + wt;
-                        m2 = m2 + wt * x;
-                        n++;
-                    }
-                    if (hit) T *= (1.0f - hitAlpha);
+                    const float x = Pfx + tau;
+                    const float w = T * hitAlpha; // T: the transmittance before the event
+                    const float wt = w * x;
+                    m0 = m0 + w;
+                    m1 = m1 + wt;
+                    m2 = m2 + wt * x;
+                    n++;
                 }
-                if (act) {
-                    if (kb.key[K - 1] == kKeyInvalid) act = false;
-                    else last_key = kb.key[K - 1];
-                    act = act && (lastT <= seg_tmax) && (T > minT);
-                }
-            }
-            // ---- the iteration's step of the loop (shade_ray, grt_render.hip): the segment's moments enter with c_s ----
-            if (it) {
-                density = 1.0f - T;
-                const float D = density;
-                float c_s;
-                if (state == Terminate) {
-                    c_s = 1.0f;
-                    going = false;
-                } else if (state == LastGaussianPass) { // A = clamp(A + D)
-                    c_s = D * (1.0f - B);
-                    A = clampf(A + D, 0.0f, 1.0f);
-                } else { // A = clamp(A + D); B = clamp(B + D)
-                    c_s = 1.0f - A;
-                    A = clampf(A + D, 0.0f, 1.0f);
-                    B = clampf(B + D, 0.0f, 1.0f);
-                }
+            },
+            [&](const MeshSeg& s, float, float D) { // the segment's moments enter with c_s
+                const float c_s = seg_weight(s.state, s.A, s.B, D);
                 weight = weight + m0 * c_s;
                 dist = dist + m1 * c_s;
                 dist2 = dist2 + m2 * c_s;
-                if (state == Terminate && counted && k.surface != 0u) { // the surface itself, as the colour's ncol (1 - D)
+                if (s.state == Terminate && counted && k.surface != 0u) { // the surface itself, as the colour's ncol (1 - D)
                     const float u = 1.0f - D;
-                    const float xs = Pfx + seg_tmax;
+                    const float xs = Pfx + s.seg_tmax;
                     const float ux = u * xs;
                     weight = weight + u;
                     dist = dist + ux;
                     dist2 = dist2 + ux * xs;
                 }
-                Pfx = Pfx + seg_tmax;
-                timeout += 1;
-                if (timeout > kTimeoutIterations) going = false;
-            }
-        }
+                Pfx = Pfx + s.seg_tmax;
+            });
     }
     if (has_out) { // every element of the window or of the buffer once per requested array: zeros for a ray that was not traced
         if (k.o.dist) k.o.dist[idx] = dist;
@@ -260,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_backward_depth_mesh(const RenderArgs
             // sweep 1: the segment's weight c_s, and what lies behind it of sum_j gD_j T_end,j
             float c_s = 0.0f, G_s = 0.0f;
             if (pass) {
-                c_s = (state == Terminate) ? 1.0f : (state == LastGaussianPass ? D_fin * (1.0f - B) : 1.0f - A);
+                c_s = seg_weight(state, A, B, D_fin);
                 G_s = F_tot;
                 if (state == GaussianPass && step <= e_tot) G_s += K0 * (TT_e - mTT) + (QT_e - mQT);
             }
@@ -394,11 +314,7 @@ static int fill(grt_ctx* c, const grt_params* p, int kind, uint32_t flags, uint3
         c->err = std::string(fn) + ": unknown flag bits " + std::to_string(flags & ~(uint32_t)GRT_DEPTH_SURFACE) + " (GRT_DEPTH_SURFACE = 1)";
         return GRT_ERR_INVALID;
     }
-    if (step_last != 0u && step_first > step_last) {
-        c->err = std::string(fn) + ": step_first > step_last (iterations are counted from 1; step_last = 0 leaves the range open)";
-        return GRT_ERR_INVALID;
-    }
-    return GRT_OK;
+    return check_step_range(c, step_first, step_last, fn);
 }
 
 static int check_forward(grt_ctx* c, const grt_depth_mesh_out* o, const char* fn)
@@ -433,7 +349,7 @@ static int launch_forward(grt_ctx* c, const RenderArgs& a, int kind, uint32_t fl
     DepthMeshFwd k;
     k.pos = sc->d_pos; k.scale = sc->d_scale; k.quat = sc->d_quat;
     k.o = *out;
-    k.first = step_first; k.last = step_last;
+    k.steps = StepRange(step_first, step_last);
     k.surface = (flags & GRT_DEPTH_SURFACE) ? 1u : 0u;
     void* args[2] = {const_cast<RenderArgs*>(&a), &k};
     const void* kernel = kind == GRT_DEPTH_PEAK ? reinterpret_cast<const void*>(k_ray_depth_mesh<true>)

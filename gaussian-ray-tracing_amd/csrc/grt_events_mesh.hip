@@ -5,38 +5,29 @@
 // over the whole ray, and the events first .. first + K - 1 go to slot n - first as (original id, key distance on the iteration's own
 // ray, alpha, iteration).  Beside them the ray's path: per iteration its ray (o_s, d_s), the end of its segment and its state.
 //
-// Both kernels: one ray per lane, an 8x8 tile or 64 buffer rays per wave; the raygen loop is k_particle_stats_mesh's (grt_stats_mesh.hip),
-// statement for statement, ONE sweep each.  The step filter is a per-lane predicate on the iteration's number: an event outside the
-// range is composited — T, A and B run through it — and is neither numbered nor listed; it changes no control flow.
-//   k_ray_events_mesh            a listed event goes to its slot by up to four plain vector stores, an iteration below P to its path
-//                                slot; after the loop the lane fills the slots behind its last listed event and behind its last
-//                                iteration and stores count, T_in and n_steps.  No atomic, no buffer of the context.  A NULL output is a
-//                                wave-uniform branch on a kernel argument.
-//   k_backward_events_mesh<MERGE> a pre-scan of the lane's column of the upstream leaves a ray whose values are all 0 untraced; a listed
-//                                event with g != 0 below the 0.99 clamp forms its 11 geometry / opacity values with dLda = g
-//                                (alpha_terms) on the ITERATION'S OWN ray (o_s, d_s), and the whole wave calls scatter<MERGE> for every
-//                                slot.  dloss/dalpha is the caller's, so nothing depends on D_S: one sweep, which a lane leaves at the
-//                                end of the round that holds its last non-zero slot.  It launches through
-//                                bwd_launch with EvMeshUp behind (RenderArgs, BwdArgs): gradient buffer and flush.
-//
-// Wave convergence: scatter<MERGE> (DPP, v_readlane) is reached by every lane of the wave for every slot of every round of every
-// iteration.  The three nested loops (iterations, rounds, slots) are each entered and left on a wave-uniform condition — a ballot
-// over the lanes' own conditions, or a constant trip count — and a lane whose own condition is false idles inside them with
-// `it` / `act` cleared, as the header of grt_backward_mesh.hip states.  The mesh walk is the per-lane mesh_closest_t and the k-nearest
-// round the per-lane gps_round, both inside `if (it)` / `if (act)` and neither with a wave operation in it; the forward's stores and
-// its two fill loops behind the raygen loop are per lane and hold no wave operation either.  Why it cannot hang: a lane's iterations
-// are bounded by max_bounces and the 1000-iteration timeout, its rounds by lastT rising past the segment's end (a round that finds
-// nothing clears `act`), the slot loop runs K times, and the group loop of wave_groups inside scatter clears at least its leader's bit
-// of a ballot per turn — every ballot becomes zero.  Only vector stores and vector atomics write memory.
+// Both kernels: one ray per lane, an 8x8 tile or 64 buffer rays per wave, ONE sweep of the raygen loop each (grt_mesh_walk.h: the loop,
+// its convergence contract and why it cannot hang).  The step filter is a per-lane predicate on the iteration's number: an event
+// outside the range is composited — T, A and B run through it — and is neither numbered nor listed; it changes no control flow.
+//   k_ray_events_mesh            keeps the loop WRITTEN OUT as it had it, its own step filter included, statement for statement mesh_walk's and sweep_events' (a change there is a
+//                                change here): its seven NULL tests are seven lane masks, it sits at the 106-SGPR limit, and on mesh_walk
+//                                it read two more spilled SGPRs back per iteration than tests/test_picks_events_mesh_isa.py allows
+//                                (DESIGN.md 5.27).  A listed event goes to its slot by up to four plain vector stores, an iteration
+//                                below P to its path slot; after the loop the lane fills the slots behind its last listed event and
+//                                behind its last iteration and stores count, T_in and n_steps.  No atomic, no buffer of the context,
+//                                no wave operation but the loops' ballots.  A NULL output is a wave-uniform branch on a kernel argument.
+//   k_backward_events_mesh<MERGE> on mesh_walk.  A pre-scan of the lane's column of the upstream leaves a ray whose values are all 0
+//                                untraced; a listed event with g != 0 below the 0.99 clamp forms its 11 geometry / opacity values with
+//                                dLda = g (alpha_terms) on the ITERATION'S OWN ray (o_s, d_s), and the whole wave calls scatter<MERGE>
+//                                for every slot (on_slot).  dloss/dalpha is the caller's, so nothing depends on D_S: one sweep, which a
+//                                lane leaves (mesh_walk's `leave`) at the end of the round that holds its last non-zero slot.  It
+//                                launches through bwd_launch with EvMeshUp behind (RenderArgs, BwdArgs): gradient buffer and flush.
 #include <string>
 
-#include "grt_bwd.h"
-#include "grt_mesh.h"
+#include "grt_mesh_walk.h"
 
 namespace grt {
 namespace {
 
-static_assert(kBlock == kRoundBlock, "the mesh event kernels run gps_round (grt_kround.h): its per-lane stack stride is the launch block size");
 static_assert(GRT_STEP_LAST == LastGaussianPass && GRT_STEP_GAUSSIAN == GaussianPass && GRT_STEP_TERMINATE == Terminate,
               "path_state holds the raygen loop's own state numbers");
 
@@ -48,7 +39,7 @@ struct EvMeshUp {
     const float* g; // upstream [K][N]
     uint64_t n;     // N
     uint32_t first, max_events;
-    uint32_t step_first, step_last;
+    StepRange steps;
 };
 
 __global__ __launch_bounds__(kBlock) void k_ray_events_mesh(const RenderArgs a, const EvMeshOut k)
@@ -216,105 +207,35 @@ __global__ __launch_bounds__(kBlock) void k_backward_events_mesh(const RenderArg
     live = live && (stop_n != 0u); // a ray whose K upstream values are all exactly 0 is not traced
     if (!__builtin_amdgcn_ballot_w64(live)) return; // wave-uniform
 
-    const float epsT = 1e-9f;
-    const float minT = a.p.minTransmittance;
-    const uint64_t key0 = mk_key(a.p.t_min + epsT, 0x7FFFFFFFu, 1);
-    KBuf<K> kb;
-    grt::Cnt cnt; // (dead: no counters, no watchdog)
     RayAcc ra;    // (dead: alpha_terms<false> does not touch it)
     ra.go = ra.gd = ra.gdn = mk3(0, 0, 0);
 
     uint32_t n = 0; // this lane's composited events inside the step range so far
-    f3 curO = o, curD = d;
-    float A = 0.0f, B = 0.0f, density = 0.0f;
-    uint32_t numBounces = 0u, timeout = 0u, step = 0u;
-    bool going = live;
-    // ---- the raygen loop (shaders/tracer.cu:58-106), the whole wave in step ----
-    while (true) {
-        const bool it = going && (length3(curD) > 0.1f) && (numBounces < a.p.max_bounces);
-        going = it;
-        if (!__builtin_amdgcn_ballot_w64(it)) break; // wave-uniform
-        const f3 ray_o = curO, ray_d = curD;
-        int state = LastGaussianPass;
-        float seg_tmax = a.p.t_max;
-        f3 normal = mk3(0, 0, 0);
-        if (it) { // per lane: no wave operation inside
-            uint32_t n0 = 0, n1 = 0;
-            const MeshHit mh = mesh_closest_t<false, kBlock>(a, stk, ray_o, ray_d, kTraceMeshTmin, kTraceMeshTmax, n0, n1);
-            mesh_shade(a, mh, ray_o, ray_d, state, seg_tmax, normal, curO, curD, numBounces);
-            step++;
-        }
-        // ---- this iteration's Gaussian segment [t_min, seg_tmax] on (ray_o, ray_d), T carried on (trace(), tracer.cuh:328-373) ----
-        const rayinv ri = mk_rayinv(ray_o, ray_d);
-        const float t_hi = seg_tmax + epsT;
-        float T = 1.0f - density, lastT = a.p.t_min;
-        uint64_t last_key = key0;
-        const bool counted = (step >= u.step_first) && (u.step_last == 0u || step <= u.step_last);
-        bool act = it && (lastT <= seg_tmax) && (T > minT);
-        while (__builtin_amdgcn_ballot_w64(act)) {
-            if (act) {
-                gps_round<false, false, K>(a, stk, ray_o, ray_d, ri, last_key, t_hi, kb, cnt, 0xFFFFFFFFu);
-                if (kb.key[0] == kKeyInvalid) act = false;
-            }
-#pragma unroll 1
-            for (int i = 0; i < K; i++) {
-                bool hit = false, geom = false;
-                uint32_t id = 0;
-                float v[kVals];
+    bool counted = false;
+    mesh_walk(
+        a, stk, o, d, live, [&](const MeshSeg& s) { counted = u.steps.counted(s.step); },
+        [&](const MeshSeg& s, bool hit, uint32_t id, float, float hitAlpha, uint64_t) {
+            bool geom = false;
+            float v[kVals];
 #pragma unroll
-                for (int q = 0; q < kVals; q++) v[q] = 0.0f;
-                uint64_t key = kKeyInvalid;
-                float hitAlpha = 0.0f;
-#pragma unroll
-                for (int j = 0; j < K; j++) {
-                    if (j == i) { key = kb.key[j]; hitAlpha = kb.alpha[j]; }
-                }
-                if (act && key != kKeyInvalid && T > minT) {
-                    lastT = fmaxf(key_t(key), lastT);
-                    if (a.p.alpha_min < hitAlpha) {
-                        hit = true;
-                        id = key_id(key);
+            for (int q = 0; q < kVals; q++) v[q] = 0.0f;
+            if (hit && counted) {
+                const uint32_t slot = n - first; // (n < first wraps past K)
+                if (slot < Kn && hitAlpha < 0.99f) { // (where the 0.99 clamp binds nothing goes into opacity or geometry)
+                    const float dLda = g[(size_t)slot * N + idx];
+                    if (dLda != 0.0f) {
+                        geom = true;
+                        alpha_terms<false>(b, id, s.ray_o, s.ray_d, dLda, v, ra); // the iteration's own ray
                     }
                 }
-                if (hit && counted) {
-                    const uint32_t s = n - first; // (n < first wraps past K)
-                    if (s < Kn && hitAlpha < 0.99f) { // (where the 0.99 clamp binds nothing goes into opacity or geometry)
-                        const float dLda = g[(size_t)s * N + idx];
-                        if (dLda != 0.0f) {
-                            geom = true;
-                            alpha_terms<false>(b, id, ray_o, ray_d, dLda, v, ra); // the iteration's own ray
-                        }
-                    }
-                    n++;
-                }
-                scatter<MERGE>(b.acc, geom, id, v, geom, false, lane); // every lane of the wave
-                if (hit) T *= (1.0f - hitAlpha);
+                n++;
             }
-            if (act) {
-                if (kb.key[K - 1] == kKeyInvalid) act = false;
-                else last_key = kb.key[K - 1];
-                act = act && (lastT <= seg_tmax) && (T > minT);
-                // behind its last non-zero slot the lane has nothing left to differentiate: it leaves the walk here, between two
-                // rounds, and idles in the wave's loops like a lane whose ray has ended (a per-lane condition, as the others)
-                if (n >= stop_n) { act = false; going = false; }
-            }
-        }
-        // ---- the iteration's step of the loop (shade_ray, grt_render.hip) ----
-        if (it) {
-            density = 1.0f - T;
-            const float D = density;
-            if (state == Terminate) {
-                going = false;
-            } else if (state == LastGaussianPass) { // A = clamp(A + D)
-                A = clampf(A + D, 0.0f, 1.0f);
-            } else { // A = clamp(A + D); B = clamp(B + D)
-                A = clampf(A + D, 0.0f, 1.0f);
-                B = clampf(B + D, 0.0f, 1.0f);
-            }
-            timeout += 1;
-            if (timeout > kTimeoutIterations) going = false;
-        }
-    }
+            scatter<MERGE>(b.acc, geom, id, v, geom, false, lane); // every lane of the wave
+        },
+        [](const MeshSeg&, float, float) {},
+        // behind its last non-zero slot the lane has nothing left to differentiate: it leaves the walk between two rounds and idles in
+        // the wave's loops like a lane whose ray has ended (a per-lane condition, as the others)
+        [&]() { return n >= stop_n; });
 }
 
 } // namespace
@@ -329,10 +250,7 @@ static int fill(grt_ctx* c, const grt_params* p, bool have_range, uint32_t first
 {
     int rc = bwd_fill_args(c, p, true, a, fn);
     if (rc != GRT_OK || !have_range) return rc;
-    if (step_last != 0u && step_first > step_last) {
-        c->err = std::string(fn) + ": step_first > step_last (iterations are counted from 1; step_last = 0 leaves the range open)";
-        return GRT_ERR_INVALID;
-    }
+    if ((rc = check_step_range(c, step_first, step_last, fn)) != GRT_OK) return rc;
     if (max_events == 0) { c->err = std::string(fn) + ": max_events must be >= 1"; return GRT_ERR_INVALID; }
     if (first > 0xFFFFFFFFu - max_events) {
         c->err = std::string(fn) + ": first + max_events overflows (" + std::to_string(first) + " + " + std::to_string(max_events) + ")";
@@ -394,7 +312,7 @@ static int launch_backward(grt_ctx* c, const grt_params* p, const RenderArgs& a,
                            uint32_t step_first, uint32_t step_last, const grt_gaussian_grads* g, void* stream, const char* fn)
 {
     EvMeshUp u;
-    u.g = d_grad_alpha; u.n = plane(a); u.first = first; u.max_events = max_events; u.step_first = step_first; u.step_last = step_last;
+    u.g = d_grad_alpha; u.n = plane(a); u.first = first; u.max_events = max_events; u.steps = StepRange(step_first, step_last);
     // ([0]: a call without a geometry group is refused; no ray, no particle or an empty tree: bwd_launch writes nothing)
     static const void* const kernels[3] = {nullptr, reinterpret_cast<const void*>(k_backward_events_mesh<false>),
                                            reinterpret_cast<const void*>(k_backward_events_mesh<true>)};

@@ -9,9 +9,11 @@
 // predicate on the iteration's number: an event outside the range is composited — T, A and B run through it — with a feature row of
 // zero; it changes no control flow.
 //
-// Both kernels: one ray per lane, an 8x8 tile or 64 buffer rays per wave; the raygen loop is k_particle_stats_mesh's, statement for
-// statement.  The channel count C is a runtime argument; the channel loops run to the compile-time CP in {4, 8, 16} under the guard
-// c < C, as in grt_features.hip.
+// Both kernels: one ray per lane, an 8x8 tile or 64 buffer rays per wave.  Both keep the raygen loop WRITTEN OUT as they had it before
+// grt_mesh_walk.h, statement for statement mesh_walk's and sweep_events' (that header: the loop, its convergence contract and why it
+// cannot hang; a change there is a change here), their own step filter included: on mesh_walk the 16-channel instantiations ran 0.9 to
+// 1.4 % behind.  The channel count C is a runtime argument; the channel loops run to the compile-time CP in
+// {4, 8, 16} under the guard c < C, as in grt_features.hip.
 //   k_render_features_mesh<CP>   ONE sweep: the last pass's c_S = D_S (1 - B_{S-1}) is needed only when that segment ends, where D_S
 //                                is known.  Two sets of CP accumulators, Phi_s and F; plain stores at the end, no atomic.
 //   k_backward_features_mesh<MERGE, CP, GEOM>   two sweeps as k_backward_mesh: sweep 0 collects its seven per-lane totals and D_fin
@@ -24,22 +26,14 @@
 //                   gradient buffer and no flush are in its text.
 //
 // Wave convergence: scatter<MERGE> and feat_scatter<MERGE, CP> (DPP, v_readlane) are reached by every lane of the wave for every slot
-// of every round of every iteration.  The three nested loops (iterations, rounds, slots) are each entered and left on a wave-uniform
-// condition — a ballot over the lanes' own conditions, or a constant trip count — and a lane whose own condition is false idles
-// inside them with `it` / `act` cleared, as the header of grt_backward_mesh.hip states.  The mesh walk is the per-lane mesh_closest_t
-// and the k-nearest round the per-lane gps_round, both inside `if (it)` / `if (act)` and neither with a wave operation in it.  Why
-// it cannot hang: a lane's iterations are bounded by max_bounces and the 1000-iteration timeout, its rounds by lastT rising past the
-// segment's end (a round that finds nothing clears `act`), the slot loop runs K times, and the group loop of wave_groups clears at
-// least its leader's bit of a ballot per turn — every ballot becomes zero.  Only vector stores and vector atomics write memory.
+// of every round of every iteration; the loops are entered and left as grt_mesh_walk.h's head states.
 #include <string>
 
-#include "grt_bwd.h"
-#include "grt_mesh.h"
+#include "grt_mesh_walk.h"
 
 namespace grt {
 namespace {
 
-static_assert(kBlock == kRoundBlock, "the mesh feature kernels run gps_round (grt_kround.h): its per-lane stack stride is the launch block size");
 static_assert(GRT_MAX_FEATURE_CHANNELS == 16, "the instantiations below are CP = 4, 8, 16");
 
 // the iterations whose events carry their feature row: first..last, 1-based, inclusive; last = 0: open
@@ -284,7 +278,7 @@ __global__ __launch_bounds__(kBlock) void k_backward_features_mesh(const RenderA
             // sweep 1: the segment's weight c_s, and what lies behind it of sum_j gD_j T_end,j
             float c_s = 0.0f, G_s = 0.0f;
             if (pass) {
-                c_s = (state == Terminate) ? 1.0f : (state == LastGaussianPass ? D_fin * (1.0f - B) : 1.0f - A);
+                c_s = seg_weight(state, A, B, D_fin);
                 if constexpr (GEOM) {
                     G_s = F_tot;
                     if (state == GaussianPass && step <= e_tot) G_s += K0 * (TT_e - mTT) + (QT_e - mQT);
@@ -411,11 +405,7 @@ static int fill(grt_ctx* c, const grt_params* p, uint32_t channels, uint32_t ste
         c->err = std::string(fn) + ": channels must be 1.." + std::to_string(GRT_MAX_FEATURE_CHANNELS) + ", not " + std::to_string(channels);
         return GRT_ERR_INVALID;
     }
-    if (step_last != 0u && step_first > step_last) {
-        c->err = std::string(fn) + ": step_first > step_last (iterations are counted from 1; step_last = 0 leaves the range open)";
-        return GRT_ERR_INVALID;
-    }
-    return GRT_OK;
+    return check_step_range(c, step_first, step_last, fn);
 }
 
 static int launch_forward(grt_ctx* c, const RenderArgs& a, const float* d_feat, uint32_t channels, float* d_out, uint32_t step_first,

@@ -501,6 +501,8 @@ int set_rays(grt_ctx* c, RenderArgs* a, const float* d_rays, uint64_t n, const c
 // refusal's parenthesis (a unit without a mesh variant says so in its own words).
 int bwd_fill_args(grt_ctx* c, const grt_params* p, bool mesh, RenderArgs* a, const char* fn,
                   const char* gauss_only = "grt_backward_mesh / grt_backward_rays_mesh differentiate mesh frames");
+// The step range of a mesh unit's call (iterations step_first .. step_last, 1-based; step_last = 0: open): refused when it ends before it begins.
+int check_step_range(grt_ctx* c, uint32_t step_first, uint32_t step_last, const char* fn);
 // The launch of a one-ray-per-lane kernel over a.n_blocks blocks (grt_bwd.h, kRoundBlock lanes each): one LDS stack per lane as deep
 // as the Gaussian tree and, where a.n_faces, the mesh tree (more than 160 KiB: GRT_ERR_LIMIT), ev0, the kernel with `args` on s.
 // lane_launch_done: the launch's error, ev1 and have_timing behind it — or behind what the caller put on s in between.

@@ -1,6 +1,6 @@
 """Device time of the differentiable ray depth of a mesh frame beside the feature channels of the same frame.
 
-    python profiles/tools/mesh_depth_timing.py        # one JSON line; kept as profiles/mesh_depth_timing.json
+    python profiles/tools/mesh_depth_timing.py [--out FILE]        # one JSON line; kept as profiles/mesh_depth_timing.json
 
 The scene is bench.py's C4 at C2's size: C2's 100 k Gaussians at 1280x720 with C4's mirror sphere and max_bounces 2.  In ONE process
 with the calls ALTERNATED round by round: grt_last_kernel_ms, median (min, max) of 20 rounds after 5, of
@@ -43,6 +43,12 @@ def build_scene():
 
 
 def main(n=20, warm=5):
+    args = sys.argv[1:]
+    out_path = None  # --out FILE: the JSON lines are appended to FILE as well
+    if "--out" in args:
+        i = args.index("--out")
+        out_path = args[i + 1]
+        del args[i:i + 2]
     acts, mesh, p, n_g, w, h, max_bounces = build_scene()
     tr = grt.Tracer(0)
     tr.upload(acts)
@@ -79,6 +85,9 @@ def main(n=20, warm=5):
         res[f"ratio_forward_{k}_to_features_c1"] = res[f"depth_mesh_forward_{k}_ms"][0] / res["features_mesh_forward_c1_ms"][0]
         res[f"ratio_backward_{k}_to_features_c1_geometry"] = res[f"depth_mesh_backward_{k}_ms"][0] / res["features_mesh_backward_c1_geometry_ms"][0]
     print(json.dumps(res), flush=True)
+    if out_path:
+        with open(out_path, "a") as f:
+            f.write(json.dumps(res) + "\n")
     tr.close()
 
 

@@ -1,6 +1,6 @@
 """Device time of the feature channels of a mesh frame beside the mesh statistics, the mesh backward and the aux frame.
 
-    python profiles/tools/mesh_feat_timing.py [C4]        # one JSON line per workload; kept as profiles/mesh_feat_timing.json
+    python profiles/tools/mesh_feat_timing.py [C4] [--out FILE]        # one JSON line per workload; kept as profiles/mesh_feat_timing.json
 
 Per workload (bench.py's scene, camera and mesh: C4 is 1 M Gaussians at 1920x1080 with the mirror sphere, max_bounces 2), in ONE
 process with the calls ALTERNATED round by round: grt_last_kernel_ms, median (min, max) of 20 rounds after 5, of
@@ -28,7 +28,13 @@ import grt  # noqa: E402
 
 
 def main(n=20, warm=5):
-    for name in sys.argv[1:] or ["C4"]:
+    args = sys.argv[1:]
+    out_path = None  # --out FILE: the JSON lines are appended to FILE as well
+    if "--out" in args:
+        i = args.index("--out")
+        out_path = args[i + 1]
+        del args[i:i + 2]
+    for name in args or ["C4"]:
         _, n_g, w, h, fisheye, with_mesh, max_bounces, _ = bench.WORKLOADS[name]
         acts, center, mesh = bench.build_scene(grt, name)
         p = grt.default_params(w, h, center, fisheye=fisheye, mesh_type=grt.MIRROR, max_bounces=max_bounces)
@@ -68,6 +74,9 @@ def main(n=20, warm=5):
         res["ratio_forward_c16_to_count_only"] = res["features_mesh_forward_c16_ms"][0] / res["stats_mesh_count_only_ms"][0]
         res["ratio_backward_all_five_to_backward_mesh"] = res["features_mesh_backward_c16_all_five_ms"][0] / res["backward_mesh_ms"][0]
         print(json.dumps(res), flush=True)
+        if out_path:
+            with open(out_path, "a") as f:
+                f.write(json.dumps(res) + "\n")
         tr.close()
 
 
