@@ -170,6 +170,22 @@ class DepthMeshUpstream(C.Structure):
     _fields_ = [("g_dist", C.c_void_p), ("g_dist2", C.c_void_p), ("g_weight", C.c_void_p)]
 
 
+class PointOut(C.Structure):
+    """grt_point_out (include/grt.h): device pointers of density / occupancy / peak / peak_id / count [n], each may be NULL, not all."""
+    _fields_ = [(n, C.c_void_p) for n in ("density", "occupancy", "peak", "peak_id", "count")]
+
+
+class PointUpstream(C.Structure):
+    """grt_point_upstream (include/grt.h): device pointers of dloss/ddensity and dloss/doccupancy [n], each may be NULL, not both."""
+    _fields_ = [("g_density", C.c_void_p), ("g_occupancy", C.c_void_p)]
+
+
+class PointGrads(C.Structure):
+    """grt_point_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity (added to) and points [n][3]
+    (written); each may be NULL, not all."""
+    _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "points")]
+
+
 class FeatureGrads(C.Structure):
     """grt_feature_grads (include/grt.h): device pointers of the gradient arrays pos, scale, quat, opacity, feat; each may be NULL."""
     _fields_ = [(n, C.c_void_p) for n in ("pos", "scale", "quat", "opacity", "feat")]
@@ -204,6 +220,8 @@ DEPTH_KINDS = {"key": 0, "peak": 1}  # GRT_DEPTH_KEY, GRT_DEPTH_PEAK
 DEPTH_GROUPS = ("pos", "scale", "quat", "opacity")
 DEPTH_MESH_OUTPUTS = ("dist", "dist2", "weight", "count")
 DEPTH_SURFACE = 1  # GRT_DEPTH_SURFACE
+POINT_OUTPUTS = ("density", "occupancy", "peak", "peak_id", "count")
+POINT_GROUPS = ("pos", "scale", "quat", "opacity")
 
 
 class Mesh(C.Structure):
@@ -247,7 +265,7 @@ EXPORTS = [
     "grt_ray_depth_frame", "grt_ray_depth_rays", "grt_backward_depth_frame", "grt_backward_depth_rays",
     "grt_ray_depth_mesh_frame", "grt_ray_depth_mesh_rays", "grt_backward_depth_mesh_frame", "grt_backward_depth_mesh_rays",
     "grt_render_features_frame", "grt_render_features_rays", "grt_backward_features_frame", "grt_backward_features_rays", "grt_render_features_mesh_frame", "grt_render_features_mesh_rays",
-    "grt_backward_features_mesh_frame", "grt_backward_features_mesh_rays", "grt_sync",
+    "grt_backward_features_mesh_frame", "grt_backward_features_mesh_rays", "grt_query_points", "grt_backward_points", "grt_sync",
     "grt_get_counters", "grt_last_kernel_ms", "grt_host_activate", "grt_host_uvw_frame", "grt_host_synth_scene",
     "grt_host_ply_count", "grt_host_ply_read", "grt_host_ply_write", "grt_host_last_error",
     "grt_host_primitive_counts", "grt_host_primitive_fill", "grt_host_obj_count", "grt_host_obj_read", "grt_host_obj_write",
@@ -343,6 +361,8 @@ def lib():
         L.grt_render_features_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, u32, u32, vp]
         L.grt_backward_features_mesh_frame.argtypes = [vp, C.POINTER(Params), vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, u32, u32, u32, u32, vp]
         L.grt_backward_features_mesh_rays.argtypes = [vp, C.POINTER(Params), vp, u64, vp, u32, vp, C.POINTER(FeatureGrads), u32, u32, vp]
+        L.grt_query_points.argtypes = [vp, vp, u64, fl, C.POINTER(PointOut), vp]
+        L.grt_backward_points.argtypes = [vp, vp, u64, fl, C.POINTER(PointUpstream), C.POINTER(PointGrads), vp]
         L.grt_sync.argtypes = [vp]
         L.grt_sync.restype = C.c_int
         L.grt_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -1500,6 +1520,84 @@ class Tracer:
                                                                steps[0], steps[1], x0, y0, x1, y1, self._stream()))
             if gf is not None and sliced:
                 into["feat"][:, c0:c0 + MAX_FEATURE_CHANNELS] += gf
+        return into
+
+    def _point_inputs(self, what, points, alpha_min):
+        """points [n][3] as a contiguous float32 tensor on the tracer's GPU, the device, and alpha_min as the library takes it (0: the
+        scene's own)."""
+        t = self._torch
+        dev = t.device("cuda", self.device)
+        if not t.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+            raise GrtError(f"{what}: points must be a tensor of shape [n][3]")
+        return points.detach().to(dev, t.float32).contiguous(), dev, (0.0 if alpha_min is None else float(alpha_min))
+
+    def query_points(self, points, alpha_min=None, outputs=POINT_OUTPUTS):
+        """grt_query_points: the Gaussian field at points [n][3] -> dict of torch tensors [n] on the tracer's GPU: 'density' (sum of the
+        contributing particles' a_i = min(0.99, opacity response)), 'occupancy' (1 - prod (1 - a_i)), 'peak' (max a_i), 'peak_id'
+        (uint32: the original id of the maximum, the lowest of equal ones, PICK_NONE where nothing contributes) and 'count' (uint32);
+        include/grt.h.  A particle contributes where a_i > alpha_min (None: the scene's own; a larger value is allowed, a smaller one
+        refused).  A non-finite point and one outside every leaf box hold 0, 0, 0, PICK_NONE, 0.  Meshes are ignored.  Bitwise
+        reproducible.  Pass the points in a spatially coherent order (grid order is one): one point per lane."""
+        t = self._torch
+        points, dev, amin = self._point_inputs("query_points", points, alpha_min)
+        outputs = tuple(outputs)
+        if not outputs or any(k not in POINT_OUTPUTS for k in outputs):
+            raise GrtError(f"query_points: outputs must be a non-empty subset of {POINT_OUTPUTS}, not {outputs}")
+        n = int(points.shape[0])
+        out = {k: (t.zeros((n,), dtype=t.int32, device=dev).view(t.uint32) if k in ("peak_id", "count")
+                   else t.zeros((n,), dtype=t.float32, device=dev)) for k in POINT_OUTPUTS if k in outputs}
+        if not n:  # (no point: nothing to write)
+            return out
+        ptrs = PointOut(*(out[k].data_ptr() if k in out else None for k in POINT_OUTPUTS))
+        self._check(lib().grt_query_points(self._h, points.data_ptr(), n, amin, C.byref(ptrs), self._stream()))
+        return out
+
+    def backward_points(self, points, grad_density=None, grad_occupancy=None, alpha_min=None, into=None, groups=None, point_grads=False):
+        """grt_backward_points: grad_density, grad_occupancy [n] (each may be None, not both) hold dloss/ddensity and dloss/doccupancy
+        of what query_points computed (same points, alpha_min) -> dict of torch tensors pos, scale, quat, opacity: the gradients with
+        respect to the uploaded Gaussians, allocated zeroed for `groups` (default: all four) or ACCUMULATED into the tensors of `into`.
+        point_grads: the dict also holds "points" [n][3] (dloss/dx), WRITTEN and bitwise reproducible; groups=[] with point_grads is
+        the points-only call (no atomics, no gradient buffer).  A point whose two upstream values are exactly 0 is not walked;
+        include/grt.h."""
+        t = self._torch
+        points, dev, amin = self._point_inputs("backward_points", points, alpha_min)
+        n = int(points.shape[0])
+        ups = []
+        for name, g in (("grad_density", grad_density), ("grad_occupancy", grad_occupancy)):
+            if g is not None and (not t.is_tensor(g) or tuple(g.shape) != (n,)):
+                raise GrtError(f"backward_points: {name} must be a tensor of shape [{n}]")
+            ups.append(g.detach().to(dev, t.float32).contiguous() if g is not None else None)
+        if all(g is None for g in ups):
+            raise GrtError("backward_points: no upstream (grad_density and grad_occupancy are both None)")
+        if any(k not in POINT_GROUPS for k in (groups or ())):  # (an 'sh' tensor in `into` is handed on and left untouched)
+            raise GrtError(f"backward_points: the gradient groups are {POINT_GROUPS} (a density has no colour)")
+        if groups is None and into is None:
+            groups = POINT_GROUPS
+        pts_t = None
+        if into is not None:
+            into = dict(into)
+            pts_t = into.pop("points", None)
+            point_grads = point_grads or pts_t is not None
+        if into is None and not len(groups):
+            into = {}
+        if into is not None and not into and not point_grads:
+            raise GrtError("backward_points: no gradient group asked for")
+        into, hold = self._grad_buffers(into, groups, dev)
+        into = dict(into)
+        if point_grads:
+            if pts_t is None:
+                pts_t = t.zeros((n, 3), dtype=t.float32, device=dev)
+            elif tuple(pts_t.shape) != (n, 3) or pts_t.dtype != t.float32 or not pts_t.is_contiguous() or pts_t.device != dev:
+                raise GrtError(f"backward_points: gradient tensor 'points' must be contiguous float32 of shape {(n, 3)} on {dev}")
+            into["points"] = pts_t
+        n_part = self._scene.n_particles if self._scene is not None else self.n_particles
+        # (no point: nothing to write.  An empty scene has no gradient array to point at, so only a call with the points' output goes
+        # to the library, which WRITES that output's zeros)
+        if not n or (not n_part and not point_grads):
+            return into
+        g = PointGrads(*((getattr(hold, k) if n_part else None) for k in POINT_GROUPS), pts_t.data_ptr() if point_grads else None)
+        up = PointUpstream(*(u.data_ptr() if u is not None else None for u in ups))
+        self._check(lib().grt_backward_points(self._h, points.data_ptr(), n, amin, C.byref(up), C.byref(g), self._stream()))
         return into
 
     def _ex_buffers(self, into, groups, dev, ray_shape):

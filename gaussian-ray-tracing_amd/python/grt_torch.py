@@ -43,6 +43,12 @@ transmittance behind it, differentiable with respect to the five tensors and to 
 gives every whole ray's distance moments: dist / (1 - T_out) is the mean depth at the particles' maximum response,
 differentiable with respect to the four geometry tensors, to `rays` and to the camera — a LiDAR or monocular-depth loss, a variance
 regulariser, pose refinement from a depth map.
+
+    density, occupancy, peak, peak_id, count = grt_torch.point_field(tracer, points, geometry=(pos, scale, quat, opacity))
+
+asks about POINTS of space and not about rays: the sum and the union of the particles' alpha at every point, the
+strongest particle and the count — marching cubes over occupancy, collision queries, 3-D regularisers; density and occupancy are
+differentiable with respect to the four geometry tensors and to `points`.
 """
 import numpy as np
 import torch
@@ -637,3 +643,67 @@ def ray_depth(tracer, params, geometry=None, rays=None, camera=None, kind="peak"
             out = tracer.ray_depth(params, rays=rays, window=window, kind=kind)
         return tuple(out[k] for k in grt.DEPTH_OUTPUTS)
     return _RayDepth.apply(*gs, rays, cam_rays, window, kind, tracer, params)
+
+
+class _PointField(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, scale, quat, opacity, points, alpha_min, tracer):
+        # pos .. opacity: the tensors of the tracer's last upload, or None: only the carriers of the gradients
+        ctx.scene = tracer._scene if tracer._scene is not None else tracer  # (a view queries its parent's scene: its uploads count)
+        ctx.upload_id = ctx.scene.n_uploads
+        ctx.tracer, ctx.alpha_min = tracer, alpha_min
+        ctx.points = points.detach().to(f"cuda:{tracer.device}", torch.float32).contiguous()
+        ctx.points_like = (points.device, points.dtype)
+        ctx.like = tuple((t.device, t.dtype) if t is not None else None for t in (pos, scale, quat, opacity))
+        out = tracer.query_points(ctx.points, alpha_min=alpha_min)
+        ctx.mark_non_differentiable(out["peak"], out["peak_id"], out["count"])
+        return tuple(out[k] for k in grt.POINT_OUTPUTS)
+
+    @staticmethod
+    def backward(ctx, g_D, g_O, g_peak, g_id, g_count):
+        tr = ctx.tracer
+        if ctx.scene.n_uploads != ctx.upload_id:
+            raise grt.GrtError("grt_torch: the tracer has received another upload since this forward; its backward would differentiate "
+                               "the wrong scene (call backward before the next render on the same tracer, or use one tracer per graph)")
+        names = ("pos", "scale", "quat", "opacity")
+        groups = [n for n, want in zip(names, ctx.needs_input_grad[:4]) if want]
+        want_points = ctx.needs_input_grad[4]
+        ups = [g.to(f"cuda:{tr.device}", torch.float32).contiguous() if g is not None else None for g in (g_D, g_O)]
+        if (not groups and not want_points) or all(g is None for g in ups):
+            return (None,) * 7
+        g = tr.backward_points(ctx.points, *ups, alpha_min=ctx.alpha_min, groups=groups, point_grads=bool(want_points))  # (no group wanted: the points-only kernel)
+        out = tuple(g[n].to(*like) if n in g else None for n, like in zip(names, ctx.like))
+        return out + (g["points"].to(*ctx.points_like) if want_points else None, None, None)
+
+
+def point_field(tracer, points, geometry=None, alpha_min=None):
+    """(density, occupancy, peak, peak_id, count) of the Gaussian field at points [n][3] (Tracer.query_points; include/grt.h:
+    grt_query_points): with a_i = min(0.99, opacity response) of the particles that contribute at the point (a_i >
+    alpha_min; None: the scene's own), density = sum a_i, occupancy = 1 - prod (1 - a_i), peak = max a_i with its original id, and
+    the number of contributors.  Meshes set on the tracer are ignored.  Pass the points in a spatially coherent order (grid order).
+    Without `geometry` and with `points` not requiring grad it is the plain call under torch.no_grad().  density and occupancy are
+    differentiable with respect to geometry=(pos, scale, quat, opacity) through the kernel (grt_backward_points), the contributing set
+    held fixed, and with respect to `points` when it requires grad: the gradient arrives where and as the leaf lives (CUDA float32 or
+    CPU float64).  peak, peak_id and count carry no gradient.
+    It queries the scene the tracer HOLDS and uploads nothing, like render_features: the `geometry` tensors only carry the gradient —
+    they must be the tensors of the tracer's last upload, their shapes are checked against the tracer's particle count and their
+    values are not read.  The backward raises GrtError when the tracer has received another upload since the forward."""
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"grt_torch.point_field: points must be a tensor of shape [n][3], not {tuple(points.shape) if torch.is_tensor(points) else type(points)}")
+    gs = (None,) * 4
+    if geometry is not None:
+        gs = tuple(geometry)
+        scene = tracer._scene if tracer._scene is not None else tracer  # (a view queries its parent's scene)
+        n = scene.n_particles
+        want = {"pos": (n, 3), "scale": (n, 3), "quat": (n, 4), "opacity": (n,)}
+        if len(gs) != 4 or any(not torch.is_tensor(t) for t in gs):
+            raise ValueError("grt_torch.point_field: geometry must be four tensors (pos, scale, quat, opacity)")
+        for (name, shape), t in zip(want.items(), gs):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"grt_torch.point_field: geometry tensor '{name}' must have shape {shape} (the tracer's last upload), "
+                                 f"not {tuple(t.shape)}")
+    if geometry is None and not points.requires_grad:
+        with torch.no_grad():
+            out = tracer.query_points(points, alpha_min=alpha_min)
+        return tuple(out[k] for k in grt.POINT_OUTPUTS)
+    return _PointField.apply(*gs, points, alpha_min, tracer)

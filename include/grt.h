@@ -1132,6 +1132,66 @@ GRT_API int grt_backward_depth_mesh_frame(grt_ctx* ctx, const grt_params* p, int
 GRT_API int grt_backward_depth_mesh_rays(grt_ctx* ctx, const grt_params* p, const float* d_rays, uint64_t n, int kind, uint32_t flags,
                                          const grt_depth_mesh_upstream* up, const grt_feature_grads* grads, uint32_t step_first,
                                          uint32_t step_last, void* stream);
+/* ---- point queries: density, occupancy and owner at 3-D points, with gradients ----
+ * Every call above answers a question about a ray.  These two answer one about a POINT x of space: how much Gaussian mass lies
+ * here, is the point occupied, which particle owns it (marching cubes over an opacity field, occupancy grids and collision
+ * queries, placing a mesh outside dense matter, cropping, floater pruning by local density, 3-D regularisers on the field).
+ * For particle i with the uploaded (activated) pos mu, scale, quat, opacity o and A = diag(1/scale) R^T as the proxy records hold
+ * it (the A of grt_ray_depth_frame above):
+ *     y = A (x - mu),   r = exp(-|y|^2 / 2)  (the arithmetic of computeResponse, shaders/tracer.cuh:187-214, at d = 0),
+ *     a_i(x) = min(0.99, o r)                (the hit alpha of grt_render, shaders/tracer.cuh:354-357)
+ * and particle i CONTRIBUTES at x iff a_i(x) > alpha_min.  A particle with o <= alpha_min never contributes.
+ *   alpha_min   0 = the scene's own (grt_build_bvh's).  A value ABOVE the scene's is allowed; one below it is refused: the proxies
+ *               (inradius sqrt(2 log(o / alpha_min)) in Gaussian space) do not cover that set, and the call promises the exact set.
+ * FORWARD.  Per point, over its contributing particles, [n] each, device pointers, each may be NULL, not all:
+ *     density    sum_i a_i
+ *     occupancy  1 - prod_i (1 - a_i)        in [0, 1]; independent of the order in exact arithmetic
+ *     peak       max_i a_i
+ *     peak_id    the ORIGINAL id of that maximum; of equal maxima the lowest id; GRT_PICK_NONE where nothing contributes
+ *     count      contributing particles (uint32)
+ * A point with a non-finite coordinate, or one that lies in no leaf box of the tree, writes 0, 0, 0, GRT_PICK_NONE, 0.  Every element
+ * of every requested array is WRITTEN exactly once.  A split particle counts once (exactly one of its pieces owns a point).  No
+ * atomic, no buffer of the context: the same bits from call to call on one tree.  Meshes set on the context are IGNORED (a density
+ * does not bounce).  One point per lane: pass points in a SPATIALLY COHERENT order (grid order is one) — the lanes of a wave walk
+ * the tree independently and diverge otherwise; the result does not depend on the order.
+ * BACKWARD of loss = sum_x g_D density + g_O occupancy, the contributing set held fixed as grt_backward holds every discrete decision:
+ *     dloss/da_i = g_D + g_O V / (1 - a_i),   V = prod_j (1 - a_j)   re-derived by a first walk (the forward's outputs are no arguments)
+ * and below a_i the chain of grt_backward with v = mu - x; where the 0.99 clamp binds nothing goes into opacity, geometry or the point.
+ *   up      g_density, g_occupancy: [n] float32, each may be NULL (zero), not both.  A point whose two values are exactly 0 is not
+ *           walked.
+ *   grads   pos, scale, quat, opacity: ADDED to, by original id, through the context's gradient buffer and its flush as in
+ *           grt_backward (float atomics, not bitwise reproducible).
+ *           points [n][3]: WRITTEN once per point with plain stores, dloss/dx = -sum_i m_i with m_i = A^T g_p,i, the value that goes
+ *           to pos; exact zeros for a point that is not walked.  BITWISE reproducible, with and without the Gaussians' arrays; a
+ *           call with points alone allocates no gradient buffer.
+ * peak, peak_id and count carry no gradient.
+ * Both: asynchronous on `stream`; grt_last_kernel_ms reports the call's device time; a view queries its parent's scene.  With n = 0
+ * or an empty tree the calls return GRT_OK: the forward writes the zeros row, the backward zeros into points only.
+ * Refused with GRT_ERR_INVALID (the entry point's name in front; the context stays usable, nothing is written): NULL points with
+ * n > 0, no BVH, no output (forward: out NULL or all five arrays NULL; backward: grads NULL or all five arrays NULL), no upstream
+ * (up NULL or both NULL), alpha_min below the scene's or not finite.  GRT_ERR_LIMIT: a tree too tall for the per-lane stack, as in
+ * grt_backward. */
+typedef struct grt_point_out {      /* device pointers, [n] each, each may be NULL, not all */
+    float* density;
+    float* occupancy;
+    float* peak;
+    uint32_t* peak_id;
+    uint32_t* count;
+} grt_point_out;
+typedef struct grt_point_upstream { /* device pointers, [n] float32 each; each may be NULL (zero), not both */
+    const float* g_density;
+    const float* g_occupancy;
+} grt_point_upstream;
+typedef struct grt_point_grads {    /* device pointers, each may be NULL, not all */
+    float* pos;                     /* [N][3] added to */
+    float* scale;                   /* [N][3] added to */
+    float* quat;                    /* [N][4] added to */
+    float* opacity;                 /* [N]    added to */
+    float* points;                  /* [n][3] written */
+} grt_point_grads;
+GRT_API int grt_query_points(grt_ctx* ctx, const float* d_points, uint64_t n, float alpha_min, const grt_point_out* out, void* stream);
+GRT_API int grt_backward_points(grt_ctx* ctx, const float* d_points, uint64_t n, float alpha_min, const grt_point_upstream* up,
+                                const grt_point_grads* grads, void* stream);
 /* Waits for the context's stream and the last frame launched through this context (whatever stream it went to), then
  * reads the sticky device error word: GRT_ERR_LIMIT (text in grt_last_error, word cleared) when a wave had to give up on
  * live rays since the last check — the reference throws on traversal trouble (src/Exception.h:31-80). */
